@@ -290,7 +290,7 @@ unsigned long long hipk_seq_issued(hipk_ctx *ctx) { (void)ctx; return 0; }
 int hipk_wait_seq(hipk_ctx *ctx, unsigned long long seq) { (void)ctx; (void)seq; return 0; }
 
 /* One eigenpair of the arrowhead matrix [diag(theta) z; z' alpha] through the secular equation: the plain-C restatement of
- * rr_arrow_kernel (csrc/hipk_panels.hip; include/primme_amd_kernels.h: hipk_rr_arrow).  Same formulas, sequential sums. */
+ * rr_arrow_kernel (csrc/hipk_ritz.hip; include/primme_amd_kernels.h: hipk_rr_arrow).  Same formulas, sequential sums. */
 int hipk_rr_arrow(hipk_ctx *ctx, const hipk_rr_in *in, const double *fov, int nfov, const double *alpha_dev, double *out) {
    (void)ctx;
    if (!in || in->k < 1 || in->k > 16 || in->L < 0 || in->L > 10) return -1;
@@ -335,7 +335,7 @@ int hipk_rr_arrow(hipk_ctx *ctx, const hipk_rr_in *in, const double *fov, int nf
       const int neg = hi == 0.0;
       double mu = 0.5 * (lo + hi);
       int it = 0;
-      /* the pole at the origin exact, the rest of the sum by its tangent: a quadratic per step (csrc/hipk_panels.hip) */
+      /* the pole at the origin exact, the rest of the sum by its tangent: a quadratic per step (csrc/hipk_ritz.hip) */
       for (; it < 100; it++) {
          double S = 0.0, Sp = 0.0;
          for (int j = 0; j < k; j++) if (j != o) { const double r = 1.0 / ((th[j] - th[o]) - mu), t = z[j] * z[j] * r; S += t; Sp += t * r; }
@@ -680,7 +680,7 @@ int hipk_csr_matvec_shifted(hipk_csr *A, void *stream, const void *x, int64_t ld
          st_(A->dt, (void *)colp(A->dt, y, ldy, c), i, ld_(A->dt, colp(A->dt, y, ldy, c), i) - shift[c] * ld_(A->dt, colp(A->dt, x, ldx, c), i));
    return rc;
 }
-/* The scalar recurrences of one block-QMR step (csrc/hipk_panels.hip: qmr_alpha_dev / qmr_coeffs_dev; csrc/eigs_jd.c evaluates the
+/* The scalar recurrences of one block-QMR step (csrc/hipk_vec.hip: qmr_alpha_dev / qmr_coeffs_dev; csrc/eigs_jd.c evaluates the
  * same expressions on the host).  ISO C: every operation rounded on its own. */
 static void qmr_alpha_cpu(const double *tri, int nx, int col, double rho_prev, double eps, double *alpha, double *xr) {
    *xr = tri[col];

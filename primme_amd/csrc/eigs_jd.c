@@ -493,7 +493,7 @@ static int inner_solve(pa_solver *s, int blockSize, char *x, char *r, const doub
        * in the prologue of the launch that applies them (hipk_axpy_proj_dot_jacobi_dev, hipk_qmr_update_dir_dev), the host
        * enqueues all three, waits ONCE and then evaluates the same expressions on the mirrored reductions (the code below,
        * unchanged) for its own bookkeeping: the stopping tests, the columns that leave the block, the next step's state.
-       * Same roundings on both sides (hipk_panels.hip: qmr_alpha_dev), so the history is the three-wait sequence's, bit for bit.
+       * Same roundings on both sides (hipk_vec.hip: qmr_alpha_dev), so the history is the three-wait sequence's, bit for bit.
        * PRIMME_AMD_QMR_THREE_WAITS=1 keeps that sequence (A/B knob).  Needs reductions that stay on the device. */
       const int onewait = !three_waits && early_rho && fold_x && numIts + 1 < maxIterations && blockSize <= 8 &&
                           !(s->parallel && !s->dev_comm) && 3 * 64 + 3 * 8 < s->red_cap;

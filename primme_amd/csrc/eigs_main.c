@@ -902,7 +902,7 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
    }
 
    /* the basis never grows beyond the space itself, whatever maxBasisSize says */
-   /* (real panels: the wide-basis restart kernel takes 1 023 columns since round 6, hipk_panels.hip:ritz_big_kernel; the complex
+   /* (real panels: the wide-basis restart kernel takes 1 023 columns since round 6, hipk_ritz.hip:ritz_big_kernel; the complex
     * update stages its coefficient block in slices of 64 basis columns and its outputs in groups of 16, hipk_complex.hip:zritz_t,
     * so it takes the same width; the reference has no limit, primme_c.c:470-487) */
    const int max_basis = 1023;

@@ -21,7 +21,7 @@
 template <typename R> struct __attribute__((aligned(2 * sizeof(R)))) cpx { R re, im; };
 struct zacc { double re, im; };
 template <typename R> __device__ __forceinline__ zacc zload(const cpx<R> *p) { const cpx<R> v = *p; return {(double)v.re, (double)v.im}; }
-/* a streamed panel element: with the non-temporal hint (as in hipk_panels.hip: the panels never stay in the Infinity
+/* a streamed panel element: with the non-temporal hint (as in hipk_panel_dev.h: the panels never stay in the Infinity
  * Cache, the hint keeps them from evicting what does).  HIPK_Z_NT=0 at build time = plain loads (A/B builds). */
 #ifndef HIPK_Z_NT
 #define HIPK_Z_NT 1
@@ -834,7 +834,7 @@ int hipk_z_axpy(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const double *alpha_hos
       ZFac a;
       for (int c = 0; c < 64; c++) { a.re[c] = c < n ? alpha_host[2 * (c0 + c)] : 0.0; a.im[c] = c < n ? alpha_host[2 * (c0 + c) + 1] : 0.0; }
       const int gx = zgrid(ctx, m, 8);
-      const size_t es = dt == HIPK_C64 ? 16 : 8;
+      const size_t es = hipk_elem_size(dt);
       const char *xp = (const char *)X + (size_t)c0 * ldX * es; char *yp = (char *)Y + (size_t)c0 * ldY * es;
       if (dt == HIPK_C64) { if (xpay) hipLaunchKernelGGL((zaxpy_kernel<double, true>), dim3(gx), dim3(HIPK_BLOCK), 0, ctx->stream, a, (const cpx<double> *)xp, ldX, (cpx<double> *)yp, ldY, n, m);
                             else hipLaunchKernelGGL((zaxpy_kernel<double, false>), dim3(gx), dim3(HIPK_BLOCK), 0, ctx->stream, a, (const cpx<double> *)xp, ldX, (cpx<double> *)yp, ldY, n, m); }

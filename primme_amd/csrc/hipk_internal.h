@@ -238,6 +238,20 @@ static inline int hipk_grid_for_rows(const hipk_ctx *ctx, int64_t m, int rows_pe
 /* ---- the complex instantiation (hipk_complex.hip); the entry points of the real files dispatch here ---- */
 #define HIPK_IS_Z(dt) ((dt) == HIPK_C64 || (dt) == HIPK_C32)
 static inline hipk_dtype hipk_real_of(hipk_dtype dt) { return dt == HIPK_C64 ? HIPK_F64 : dt == HIPK_C32 ? HIPK_F32 : dt; }
+/* bytes of one panel element */
+static inline size_t hipk_elem_size(hipk_dtype dt) { return dt == HIPK_F64 ? 8 : dt == HIPK_F32 ? 4 : dt == HIPK_C64 ? 16 : 8; }
+/* algorithmic bytes of a pass that streams `ncols` columns of m rows (what hipk_prof_scope is told) */
+static inline double hipk_stream_bytes(hipk_dtype dt, int64_t m, double ncols) {
+   return (double)m * (double)(HIPK_IS_Z(dt) ? 2 : 1) * (dt == HIPK_F64 || dt == HIPK_C64 ? 8.0 : 4.0) * ncols;
+}
+/* run the statement once with T = the real scalar type of dt; any other dt ends the calling function with -44
+ * (variadic only so that the statement may hold template argument lists) */
+#define DISPATCH_RT(dt, ...)                               \
+   switch (dt) {                                           \
+   case HIPK_F64: { typedef double T; __VA_ARGS__; } break; \
+   case HIPK_F32: { typedef float T; __VA_ARGS__; } break;  \
+   default: return -44;                                    \
+   }
 int hipk_z_panel_dots(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const hipk_seg *segs, int nseg, const void *X, int64_t ldX, int nx,
       double *out_dev, int ldout);
 int hipk_z_panel_project(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const hipk_seg *segs, int nseg, const double *coef, int ldcoef,

@@ -1,0 +1,1041 @@
+/* hipk_ritz.hip — the fused Ritz / residual / restart update kernels of the outer iteration and the small
+ * Rayleigh-Ritz tail (gfx950).  The helpers shared with hipk_panels.hip (lane vectors, streamed loads, alignment
+ * tests) are in hipk_panel_dev.h.  What each kernel replaces in the reference is listed in
+ * include/primme_amd_kernels.h.
+ */
+#include "hipk_panel_dev.h"
+#include <vector>
+
+/* ================= fused Ritz / residual / restart update ===================== */
+#define RITZ_MAXOUT 80   /* per list (XV, XW) */
+#define RITZ_MAXRES 16
+struct RitzArgs {
+   int nxv, nxw, nres;
+   unsigned char xv_col[RITZ_MAXOUT], xw_col[RITZ_MAXOUT], res_col[RITZ_MAXRES];
+   short res_slot[RITZ_MAXRES];
+   void *xv_dst[RITZ_MAXOUT], *xw_dst[RITZ_MAXOUT], *res_dst[RITZ_MAXRES];
+};
+
+/* PRE: load the V row AND the W row before computing anything (2*NK registers): twice the
+ * loads in flight per lane, which is what makes this kernel bandwidth- instead of latency-bound
+ * (measured 3.0 -> see profiles/; used for NK <= 32).  !PRE: two phases sharing one row buffer. */
+template <typename T, int NK, int NR, bool PRE>
+__global__ void __launch_bounds__(HIPK_BLOCK)
+ritz_kernel(const T *__restrict__ V, const T *__restrict__ W, int64_t ld, int k,
+      const double *__restrict__ h, int ldh, int nh, const double *__restrict__ theta,
+      RitzArgs ja, int64_t m, double *__restrict__ partials, int nslots) {
+   extern __shared__ double hs[];   /* hs[c*NK + j], zero padded rows j >= k */
+   for (int t = threadIdx.x; t < NK * nh; t += HIPK_BLOCK) {
+      int c = t / NK, j = t % NK;
+      hs[t] = (j < k) ? h[j + (size_t)c * ldh] : 0.0;
+   }
+   __syncthreads();
+   double th[NR];
+#pragma unroll
+   for (int r = 0; r < NR; r++) th[r] = (r < ja.nres) ? theta[ja.res_col[r]] : 0.0;
+   double n2[NR];
+#pragma unroll
+   for (int r = 0; r < NR; r++) n2[r] = 0.0;
+   const bool needW = (ja.nxw > 0 || ja.nres > 0);
+
+   const int64_t stride = (int64_t)gridDim.x * HIPK_BLOCK;
+   for (int64_t i = (int64_t)blockIdx.x * HIPK_BLOCK + threadIdx.x; i < m; i += stride) {
+      double row[NK];
+      double roww[PRE ? NK : 1];
+      double xres[NR];
+#pragma unroll
+      for (int j = 0; j < NK; j++) row[j] = (j < k) ? (double)ldstream1<T, 4>(V + i + (size_t)j * ld) : 0.0;
+      if (PRE && needW) {
+#pragma unroll
+         for (int j = 0; j < NK; j++) roww[PRE ? j : 0] = (j < k) ? (double)ldstream1<T, 4>(W + i + (size_t)j * ld) : 0.0;
+      }
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+         xres[r] = 0.0;
+         if (r < ja.nres) {
+            const double *hc = hs + (int)ja.res_col[r] * NK;
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < NK; j++) s = fma(row[j], hc[j], s);
+            xres[r] = s;
+         }
+      }
+      for (int o = 0; o < ja.nxv; o++) {
+         const double *hc = hs + (int)ja.xv_col[o] * NK;
+         double s = 0.0;
+#pragma unroll
+         for (int j = 0; j < NK; j++) s = fma(row[j], hc[j], s);
+         ((T *)ja.xv_dst[o])[i] = (T)s;
+      }
+      if (needW) {
+         if (!PRE) {
+#pragma unroll
+            for (int j = 0; j < NK; j++) row[j] = (j < k) ? (double)ldstream1<T, 4>(W + i + (size_t)j * ld) : 0.0;
+         }
+         for (int o = 0; o < ja.nxw; o++) {
+            const double *hc = hs + (int)ja.xw_col[o] * NK;
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < NK; j++) s = fma(PRE ? roww[PRE ? j : 0] : row[j], hc[j], s);
+            ((T *)ja.xw_dst[o])[i] = (T)s;
+         }
+#pragma unroll
+         for (int r = 0; r < NR; r++)
+            if (r < ja.nres) {
+               const double *hc = hs + (int)ja.res_col[r] * NK;
+               double s = 0.0;
+#pragma unroll
+               for (int j = 0; j < NK; j++) s = fma(PRE ? roww[PRE ? j : 0] : row[j], hc[j], s);
+               T res = (T)fma(-th[r], xres[r], s);
+               if (ja.res_dst[r]) ((T *)ja.res_dst[r])[i] = res;
+               n2[r] = fma((double)res, (double)res, n2[r]);
+            }
+      }
+   }
+   if (nslots > 0) {
+      __shared__ double sm[HIPK_BLOCK / HIPK_WAVE][NR];
+      const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+         double v = hipk_wave_sum(n2[r]);
+         if (lane == 0) sm[wv][r] = v;
+      }
+      __syncthreads();
+      if (threadIdx.x < ja.nres && ja.res_slot[threadIdx.x] >= 0)
+         partials[(size_t)blockIdx.x * nslots + ja.res_slot[threadIdx.x]] =
+               (sm[0][threadIdx.x] + sm[1][threadIdx.x]) + (sm[2][threadIdx.x] + sm[3][threadIdx.x]);
+   }
+}
+
+
+/* General basis size (64 < k <= 255; unrestarted or user-chosen large maxBasisSize, e.g. the
+ * reference's tests/tests/test_001 with maxBasisSize 140).  Workgroup = one wave, 32 rows per
+ * tile; the tile's V (then W) rows are staged in LDS ([k][32] doubles = k/4 KB), so the update
+ * is still in place and every column is read exactly once.  The two half-waves split the
+ * outputs.  Not a roofline kernel: with k this large the small dense eigenproblem on the host
+ * dominates anyway. */
+#define RITZ_BIG_ROWS 32          /* rows per tile for k <= 255; 16 for k <= 511, 8 for k <= 1023 (round 6): k x rows doubles of LDS <= 64 KB */
+#define RITZ_BIG_MAXOUT 1024
+#define RITZ_BIG_MAXK 1023
+struct RitzBigArgs {       /* output lists live in device memory (ctx->jobtab) */
+   int nxv, nxw, nres;
+   const uint16_t *xv_col, *xw_col;
+   void *const *xv_dst, *const *xw_dst;
+   uint16_t res_col[RITZ_MAXRES];
+   short res_slot[RITZ_MAXRES];
+   void *res_dst[RITZ_MAXRES];
+};
+/* One wave per workgroup; a tile of R rows of all k columns of V (then W) sits in LDS, the 64 lanes are R rows x 64/R PARTS,
+ * part p takes the columns p, p + 64/R, ... when the tile is filled and the outputs p, p + 64/R, ... when it is multiplied.
+ * R = 32 is the round-1 kernel (k <= 255: restarts of wide bases, maxBasisSize > 64); R = 16 / 8 lift the basis to 511 / 1023
+ * columns on the same 64 KB (the reference has no limit, primme_c.c:470-487: VERDICT r05 Missing #3). */
+template <typename T, int R>
+__global__ void __launch_bounds__(64)
+ritz_big_kernel(const T *__restrict__ V, const T *__restrict__ W, int64_t ld, int k,
+      const double *__restrict__ h, int ldh, const double *__restrict__ theta, RitzBigArgs ja,
+      int64_t m, double *__restrict__ partials, int nslots) {
+   extern __shared__ double tile[];                /* tile[j*R + r] */
+   __shared__ double xres[RITZ_MAXRES][R];
+   constexpr int NP = 64 / R;
+   __shared__ double n2s[RITZ_MAXRES][NP];
+   const int lane = threadIdx.x, r = lane % R, part = lane / R;
+   const bool needW = (ja.nxw > 0 || ja.nres > 0);
+   double n2[RITZ_MAXRES];
+#pragma unroll
+   for (int q = 0; q < RITZ_MAXRES; q++) n2[q] = 0.0;
+   const int64_t ntiles = (m + R - 1) / R;
+   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+      const int64_t i = t * R + r;
+      const bool live = i < m;
+      __syncthreads();
+      for (int j = part; j < k; j += NP) tile[j * R + r] = live ? (double)V[i + (size_t)j * ld] : 0.0;
+      __syncthreads();
+      for (int o = part; o < ja.nxv + ja.nres; o += NP) {
+         const bool isres = o >= ja.nxv;
+         const int col = isres ? ja.res_col[o - ja.nxv] : ja.xv_col[o];
+         const double *hc = h + (size_t)col * ldh;
+         double s = 0.0;
+         for (int j = 0; j < k; j++) s = fma(tile[j * R + r], hc[j], s);
+         if (isres) xres[o - ja.nxv][r] = s;
+         else if (live) ((T *)ja.xv_dst[o])[i] = (T)s;
+      }
+      if (!needW) continue;
+      __syncthreads();
+      for (int j = part; j < k; j += NP) tile[j * R + r] = live ? (double)W[i + (size_t)j * ld] : 0.0;
+      __syncthreads();
+      for (int o = part; o < ja.nxw + ja.nres; o += NP) {
+         const bool isres = o >= ja.nxw;
+         const int q = o - ja.nxw;
+         const int col = isres ? ja.res_col[q] : ja.xw_col[o];
+         const double *hc = h + (size_t)col * ldh;
+         double s = 0.0;
+         for (int j = 0; j < k; j++) s = fma(tile[j * R + r], hc[j], s);
+         if (!isres) { if (live) ((T *)ja.xw_dst[o])[i] = (T)s; continue; }
+         T res = (T)fma(-theta[col], xres[q][r], s);
+         if (live) {
+            if (ja.res_dst[q]) ((T *)ja.res_dst[q])[i] = res;
+#pragma unroll
+            for (int qq = 0; qq < RITZ_MAXRES; qq++) if (qq == q) n2[qq] = fma((double)res, (double)res, n2[qq]);
+         }
+      }
+   }
+   if (nslots > 0) {
+      /* residual q was accumulated by part (nxw + q) % NP only: the other parts add zeros */
+#pragma unroll
+      for (int q = 0; q < RITZ_MAXRES; q++) {
+         double v = n2[q];
+         for (int off = R / 2; off > 0; off >>= 1) v += __shfl_down(v, off, R);
+         if (r == 0) n2s[q][part] = v;
+      }
+      __syncthreads();
+      if (lane < ja.nres && ja.res_slot[lane] >= 0) {
+         double v = 0.0;
+         for (int pp = 0; pp < NP; pp++) v += n2s[lane][pp];
+         partials[(size_t)blockIdx.x * nslots + ja.res_slot[lane]] = v;
+      }
+   }
+}
+
+template <typename T, int NK, bool PRE>
+static int ritz_launch_nk(hipk_ctx *ctx, int64_t m, const T *V, const T *W, int64_t ld, int k,
+      const double *h, int ldh, int nh, const double *theta, const RitzArgs &ja, int gx,
+      int nslots) {
+   size_t shm = (size_t)NK * nh * sizeof(double);
+   if (ja.nres <= 4)
+      hipLaunchKernelGGL((ritz_kernel<T, NK, 4, PRE>), dim3(gx), dim3(HIPK_BLOCK), shm, ctx->stream, V, W, ld, k, h, ldh, nh, theta, ja, m, ctx->partials, nslots);
+   else
+      hipLaunchKernelGGL((ritz_kernel<T, NK, RITZ_MAXRES, PRE>), dim3(gx), dim3(HIPK_BLOCK), shm, ctx->stream, V, W, ld, k, h, ldh, nh, theta, ja, m, ctx->partials, nslots);
+   HIPK_CHECK(hipGetLastError());
+   return 0;
+}
+
+template <typename T>
+static int ritz_dispatch(hipk_ctx *ctx, int64_t m, const T *V, const T *W, int64_t ld, int k,
+      const double *h, int ldh, int nh, const double *theta, const RitzArgs &ja, int gx, int nslots) {
+   if (k <= 8) return ritz_launch_nk<T, 8, true>(ctx, m, V, W, ld, k, h, ldh, nh, theta, ja, gx, nslots);
+   if (k <= 16) return ritz_launch_nk<T, 16, true>(ctx, m, V, W, ld, k, h, ldh, nh, theta, ja, gx, nslots);
+   if (k <= 24) return ritz_launch_nk<T, 24, true>(ctx, m, V, W, ld, k, h, ldh, nh, theta, ja, gx, nslots);
+   if (k <= 32) return ritz_launch_nk<T, 32, true>(ctx, m, V, W, ld, k, h, ldh, nh, theta, ja, gx, nslots);
+   if (k <= 48) return ritz_launch_nk<T, 48, false>(ctx, m, V, W, ld, k, h, ldh, nh, theta, ja, gx, nslots);
+   if (k <= 64) return ritz_launch_nk<T, 64, false>(ctx, m, V, W, ld, k, h, ldh, nh, theta, ja, gx, nslots);
+   return -1;
+}
+
+template <typename T>
+static int ritz_update_t(hipk_ctx *ctx, int64_t m, const T *V, const T *W, int64_t ld, int k,
+      const double *h, int ldh, const double *theta, const hipk_job *jobs, int njobs,
+      double *nrm2_dev) {
+   /* host-side job table; the small kernels take it by value, the general one from HBM */
+   struct BigTab { uint16_t xv_col[RITZ_BIG_MAXOUT], xw_col[RITZ_BIG_MAXOUT]; void *xv_dst[RITZ_BIG_MAXOUT], *xw_dst[RITZ_BIG_MAXOUT]; };
+   std::vector<char> tab_store(sizeof(BigTab));
+   BigTab &tab = *(BigTab *)tab_store.data();
+   RitzBigArgs jb_;
+   memset(&jb_, 0, sizeof(jb_));
+   int nh = 0, nslots = 0;
+   for (int q = 0; q < njobs; q++) {
+      const hipk_job &jb = jobs[q];
+      if (jb.col < 0 || jb.col > RITZ_BIG_MAXK) return -1;
+      if (jb.col + 1 > nh) nh = jb.col + 1;
+      if (jb.kind == HIPK_JOB_XV) {
+         if (jb_.nxv >= RITZ_BIG_MAXOUT) return -1;
+         tab.xv_col[jb_.nxv] = (uint16_t)jb.col; tab.xv_dst[jb_.nxv++] = jb.dst;
+      } else if (jb.kind == HIPK_JOB_XW) {
+         if (jb_.nxw >= RITZ_BIG_MAXOUT) return -1;
+         tab.xw_col[jb_.nxw] = (uint16_t)jb.col; tab.xw_dst[jb_.nxw++] = jb.dst;
+      } else if (jb.kind == HIPK_JOB_RES) {
+         if (jb_.nres >= RITZ_MAXRES) return -1;
+         jb_.res_col[jb_.nres] = (uint16_t)jb.col; jb_.res_dst[jb_.nres] = jb.dst;
+         jb_.res_slot[jb_.nres++] = (short)jb.slot;
+         if (jb.slot + 1 > nslots) nslots = jb.slot + 1;
+      } else return -1;
+   }
+   if (k <= 0 || njobs <= 0) return 0;
+   if (nslots > 0 && !nrm2_dev) return -1;
+   const bool small = (k <= 64 && jb_.nxv <= RITZ_MAXOUT && jb_.nxw <= RITZ_MAXOUT);
+   const int big_rows = k <= 255 ? RITZ_BIG_ROWS : (k <= 511 ? 16 : 8);
+   int gx = small ? hipk_grid_for_rows(ctx, m, HIPK_BLOCK * 2, 4) : hipk_grid_for_rows(ctx, m, big_rows, 8);
+   if (nslots > 0) {
+      /* every block writes every slot; slots must be 0..nslots-1, each used once */
+      if (hipk_reserve_partials(ctx, (size_t)gx * nslots)) return -2;
+   }
+   const int pslot = hipk_prof_begin(HIPK_PROF_RITZ, ctx->stream,
+         (double)m * sizeof(T) * ((double)k * (1 + ((jb_.nxw > 0 || jb_.nres > 0) ? 1 : 0)) + jb_.nxv + jb_.nxw + jb_.nres));
+   int rc;
+   if (small) {
+      RitzArgs ja;
+      memset(&ja, 0, sizeof(ja));
+      ja.nxv = jb_.nxv; ja.nxw = jb_.nxw; ja.nres = jb_.nres;
+      for (int q = 0; q < jb_.nxv; q++) { ja.xv_col[q] = (unsigned char)tab.xv_col[q]; ja.xv_dst[q] = tab.xv_dst[q]; }
+      for (int q = 0; q < jb_.nxw; q++) { ja.xw_col[q] = (unsigned char)tab.xw_col[q]; ja.xw_dst[q] = tab.xw_dst[q]; }
+      for (int q = 0; q < RITZ_MAXRES; q++) ja.res_col[q] = (unsigned char)jb_.res_col[q];
+      memcpy(ja.res_slot, jb_.res_slot, sizeof(ja.res_slot));
+      memcpy(ja.res_dst, jb_.res_dst, sizeof(ja.res_dst));
+      rc = ritz_dispatch<T>(ctx, m, V, W, ld, k, h, ldh, nh, theta, ja, gx, nslots);
+   } else {
+      const size_t shm = (size_t)k * big_rows * sizeof(double);
+      if (k > RITZ_BIG_MAXK || shm > 64 * 1024) return -1;
+      if (!ctx->jobtab) HIPK_CHECK(hipMalloc(&ctx->jobtab, sizeof(BigTab)));
+      /* the table is small and this is the rare path: staged through the context's pinned buffer and complete on return
+       * (since round 3 no runtime copy touches memory the library did not pin itself) */
+      if (hipk_upload(ctx, ctx->jobtab, &tab, sizeof(BigTab))) return -1;
+      char *dt_ = (char *)ctx->jobtab;
+      jb_.xv_col = (const uint16_t *)(dt_ + offsetof(BigTab, xv_col));
+      jb_.xw_col = (const uint16_t *)(dt_ + offsetof(BigTab, xw_col));
+      jb_.xv_dst = (void *const *)(dt_ + offsetof(BigTab, xv_dst));
+      jb_.xw_dst = (void *const *)(dt_ + offsetof(BigTab, xw_dst));
+      if (big_rows == 32) hipLaunchKernelGGL((ritz_big_kernel<T, 32>), dim3(gx), dim3(64), shm, ctx->stream, V, W, ld, k, h, ldh, theta, jb_, m, ctx->partials, nslots);
+      else if (big_rows == 16) hipLaunchKernelGGL((ritz_big_kernel<T, 16>), dim3(gx), dim3(64), shm, ctx->stream, V, W, ld, k, h, ldh, theta, jb_, m, ctx->partials, nslots);
+      else hipLaunchKernelGGL((ritz_big_kernel<T, 8>), dim3(gx), dim3(64), shm, ctx->stream, V, W, ld, k, h, ldh, theta, jb_, m, ctx->partials, nslots);
+      HIPK_CHECK(hipGetLastError());
+      rc = 0;
+   }
+   hipk_prof_end(pslot, ctx->stream);
+   if (rc) return rc;
+   if (nslots > 0) return hipk_finalize_partials(ctx, ctx->partials, gx, nslots, nrm2_dev);
+   return 0;
+}
+
+extern "C" int hipk_ritz_update(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const void *V,
+      const void *W, int64_t ldVW, int k, const double *h_dev, int ldh,
+      const double *theta_dev, const hipk_job *jobs, int njobs, double *nrm2_dev) {
+   if (HIPK_IS_Z(dt)) return hipk_z_ritz_update(ctx, dt, m, V, W, ldVW, k, h_dev, ldh, theta_dev, jobs, njobs, nrm2_dev);
+   DISPATCH_RT(dt, return ritz_update_t<T>(ctx, m, (const T *)V, (const T *)W, ldVW, k, h_dev, ldh, theta_dev, jobs, njobs, nrm2_dev));
+}
+
+/* ============ restart update + residual of the next candidate + its overlaps ============
+ * The restart pass (X = V h_c, Y = W h_c, any destinations) that also forms the residual r of ONE candidate
+ * and, in registers, its inner products with the basis it is writing: out = [ (V h)' r | Q' r | r' r |
+ * (W h)' r | W(:,k-1)' Q ] for the first nb XV / XW outputs -- what hipk_ritz_residual_overlaps delivers for the
+ * old basis, here for the restarted one, so that the iteration after a restart needs no pass of its own
+ * (reference: Num_update_VWXR in restart.c:1233-1294, then ortho.c:236-246 and update_projection.c:99-122 on the
+ * restarted basis).  One lane per row like ritz_kernel (the whole V and W row in registers before the first
+ * store, so the update may be in place); NB / QM bound the accumulators a lane carries. */
+template <typename T, int NK, int NB, int QM>
+__global__ void __launch_bounds__(HIPK_BLOCK)
+ritz_ov_kernel(const T *__restrict__ V, const T *__restrict__ W, int64_t ld, int k,
+      const double *__restrict__ h, int ldh, int nh, const double *__restrict__ theta,
+      RitzArgs ja, int nb, const T *__restrict__ Q, int64_t ldQ, int L, int64_t m, double *__restrict__ partials) {
+   extern __shared__ double hs[];   /* hs[c*NK + j], zero padded rows j >= k */
+   constexpr int QN = QM > 0 ? QM : 1;
+   for (int t = threadIdx.x; t < NK * nh; t += HIPK_BLOCK) {
+      int c = t / NK, j = t % NK;
+      hs[t] = (j < k) ? h[j + (size_t)c * ldh] : 0.0;
+   }
+   __syncthreads();
+   const int rcol = ja.res_col[0];
+   const double th = theta[rcol];
+   const double *hr = hs + rcol * NK;
+   T *rdst = (T *)ja.res_dst[0];
+   const T *wlast = W + (size_t)(k - 1) * ld;
+   double ov[NB], ow[NB], oq[QN], og[QN], n2 = 0.0;
+#pragma unroll
+   for (int o = 0; o < NB; o++) { ov[o] = 0.0; ow[o] = 0.0; }
+#pragma unroll
+   for (int l = 0; l < QN; l++) { oq[l] = 0.0; og[l] = 0.0; }
+
+   const int64_t stride = (int64_t)gridDim.x * HIPK_BLOCK;
+   for (int64_t i = (int64_t)blockIdx.x * HIPK_BLOCK + threadIdx.x; i < m; i += stride) {
+      double row[NK], roww[NK], qv[QN];
+#pragma unroll
+      for (int j = 0; j < NK; j++) row[j] = (j < k) ? (double)ldstream1<T, 4>(V + i + (size_t)j * ld) : 0.0;
+#pragma unroll
+      for (int j = 0; j < NK; j++) roww[j] = (j < k) ? (double)ldstream1<T, 4>(W + i + (size_t)j * ld) : 0.0;
+      double wl = 0.0;
+      if (QM > 0) {
+#pragma unroll
+         for (int l = 0; l < QN; l++) qv[l] = (l < L) ? (double)Q[i + (size_t)l * ldQ] : 0.0;
+         wl = (double)wlast[i];
+      }
+      double xr = 0.0, yr = 0.0;
+#pragma unroll
+      for (int j = 0; j < NK; j++) xr = fma(row[j], hr[j], xr);
+#pragma unroll
+      for (int j = 0; j < NK; j++) yr = fma(roww[j], hr[j], yr);
+      const T res = (T)fma(-th, xr, yr);
+      const double r = (double)res;
+      n2 = fma(r, r, n2);
+      /* the new basis columns: stored and multiplied with r as stored */
+#pragma unroll
+      for (int o = 0; o < NB; o++)
+         if (o < nb) {
+            const double *hv = hs + (int)ja.xv_col[o] * NK;
+            const double *hw = hs + (int)ja.xw_col[o] * NK;
+            double sv = 0.0, sw = 0.0;
+#pragma unroll
+            for (int j = 0; j < NK; j++) sv = fma(row[j], hv[j], sv);
+#pragma unroll
+            for (int j = 0; j < NK; j++) sw = fma(roww[j], hw[j], sw);
+            const T tv = (T)sv, tw = (T)sw;
+            ststream1<T, 8>((T *)ja.xv_dst[o] + i, tv);
+            ststream1<T, 8>((T *)ja.xw_dst[o] + i, tw);
+            ov[o] = fma((double)tv, r, ov[o]);
+            ow[o] = fma((double)tw, r, ow[o]);
+         }
+      for (int o = nb; o < ja.nxv; o++) {
+         const double *hc = hs + (int)ja.xv_col[o] * NK;
+         double sv = 0.0;
+#pragma unroll
+         for (int j = 0; j < NK; j++) sv = fma(row[j], hc[j], sv);
+         ststream1<T, 8>((T *)ja.xv_dst[o] + i, (T)sv);
+      }
+      for (int o = nb; o < ja.nxw; o++) {
+         const double *hc = hs + (int)ja.xw_col[o] * NK;
+         double sw = 0.0;
+#pragma unroll
+         for (int j = 0; j < NK; j++) sw = fma(roww[j], hc[j], sw);
+         ststream1<T, 8>((T *)ja.xw_dst[o] + i, (T)sw);
+      }
+      if (rdst) rdst[i] = res;
+      if (QM > 0) {
+#pragma unroll
+         for (int l = 0; l < QN; l++) { oq[l] = fma(qv[l], r, oq[l]); og[l] = fma(wl, qv[l], og[l]); }
+      }
+   }
+   /* block sums, partial-major: partials[block * nsl + slot], slots [ (Vh)'r | Q'r | r'r | (Wh)'r | W(:,k-1)'Q ] */
+   __shared__ double sm[HIPK_BLOCK / HIPK_WAVE][2 * NB + 2 * QN + 1];
+   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+   const int nsl = 2 * nb + 2 * L + 1;
+#pragma unroll
+   for (int o = 0; o < NB; o++) {
+      const double a = hipk_wave_sum(ov[o]), b = hipk_wave_sum(ow[o]);
+      if (lane == 0 && o < nb) { sm[wv][o] = a; sm[wv][nb + L + 1 + o] = b; }
+   }
+#pragma unroll
+   for (int l = 0; l < QN; l++) {
+      const double a = hipk_wave_sum(oq[l]), b = hipk_wave_sum(og[l]);
+      if (lane == 0 && QM > 0 && l < L) { sm[wv][nb + l] = a; sm[wv][2 * nb + L + 1 + l] = b; }
+   }
+   { const double a = hipk_wave_sum(n2); if (lane == 0) sm[wv][nb + L] = a; }
+   __syncthreads();
+   if ((int)threadIdx.x < nsl)
+      partials[(size_t)blockIdx.x * nsl + threadIdx.x] =
+            (sm[0][threadIdx.x] + sm[1][threadIdx.x]) + (sm[2][threadIdx.x] + sm[3][threadIdx.x]);
+}
+
+template <typename T, int NK, int NB>
+static int ritz_ov_q(hipk_ctx *ctx, int gx, size_t shm, const T *V, const T *W, int64_t ld, int k, const double *h, int ldh, int nh,
+      const double *theta, const RitzArgs &ja, int nb, const T *Q, int64_t ldQ, int L, int64_t m) {
+#define ROV(QMV) hipLaunchKernelGGL((ritz_ov_kernel<T, NK, NB, QMV>), dim3(gx), dim3(HIPK_BLOCK), shm, ctx->stream, V, W, ld, k, h, ldh, nh, theta, ja, nb, Q, ldQ, L, m, ctx->partials)
+   if (L == 0) ROV(0);
+   else if (L <= 8) ROV(8);
+   else if (L <= 16) ROV(16);
+   else if (L <= 32) ROV(32);
+   else return -1;
+#undef ROV
+   HIPK_CHECK(hipGetLastError());
+   return 0;
+}
+
+template <typename T>
+static int ritz_ov_t(hipk_ctx *ctx, int64_t m, const T *V, const T *W, int64_t ld, int k, const double *h, int ldh,
+      const double *theta, const hipk_job *jobs, int njobs, double *nrm2_dev, int nb, const T *Q, int64_t ldQ, int L,
+      double *ov_dev) {
+   if (k <= 0 || k > 32 || nb <= 0 || nb > 16 || L < 0 || L > 32 || !ov_dev) return -1;
+   RitzArgs ja;
+   memset(&ja, 0, sizeof(ja));
+   int nh = 0, res_slot = -1;
+   for (int q = 0; q < njobs; q++) {
+      const hipk_job &jb = jobs[q];
+      if (jb.col < 0 || jb.col > 255) return -1;
+      if (jb.col + 1 > nh) nh = jb.col + 1;
+      if (jb.kind == HIPK_JOB_XV) {
+         if (ja.nxv >= RITZ_MAXOUT) return -1;
+         ja.xv_col[ja.nxv] = (unsigned char)jb.col; ja.xv_dst[ja.nxv++] = jb.dst;
+      } else if (jb.kind == HIPK_JOB_XW) {
+         if (ja.nxw >= RITZ_MAXOUT) return -1;
+         ja.xw_col[ja.nxw] = (unsigned char)jb.col; ja.xw_dst[ja.nxw++] = jb.dst;
+      } else if (jb.kind == HIPK_JOB_RES) {
+         if (ja.nres >= 1) return -1;             /* one candidate */
+         ja.res_col[0] = (unsigned char)jb.col; ja.res_dst[0] = jb.dst; ja.res_slot[0] = (short)jb.slot; ja.nres = 1;
+         res_slot = jb.slot;
+      } else return -1;
+   }
+   if (ja.nres != 1 || ja.nxv < nb || ja.nxw < nb) return -1;
+   const int nsl = 2 * nb + 2 * L + 1;
+   const int gx = hipk_grid_for_rows(ctx, m, HIPK_BLOCK * 2, 4);
+   if (hipk_reserve_partials(ctx, (size_t)gx * nsl)) return -2;
+   const int pslot = hipk_prof_begin(HIPK_PROF_RITZ, ctx->stream, (double)m * sizeof(T) * (2.0 * k + L + ja.nxv + ja.nxw + (ja.res_dst[0] ? 1 : 0)));
+   int rc;
+   if (k <= 16) {
+      const size_t shm = (size_t)16 * nh * sizeof(double);
+      rc = nb <= 8 ? ritz_ov_q<T, 16, 8>(ctx, gx, shm, V, W, ld, k, h, ldh, nh, theta, ja, nb, Q, ldQ, L, m)
+                   : ritz_ov_q<T, 16, 16>(ctx, gx, shm, V, W, ld, k, h, ldh, nh, theta, ja, nb, Q, ldQ, L, m);
+   } else {
+      const size_t shm = (size_t)32 * nh * sizeof(double);
+      rc = nb <= 8 ? ritz_ov_q<T, 32, 8>(ctx, gx, shm, V, W, ld, k, h, ldh, nh, theta, ja, nb, Q, ldQ, L, m)
+                   : ritz_ov_q<T, 32, 16>(ctx, gx, shm, V, W, ld, k, h, ldh, nh, theta, ja, nb, Q, ldQ, L, m);
+   }
+   hipk_prof_end(pslot, ctx->stream);
+   if (rc) return rc;
+   if (nrm2_dev && res_slot >= 0) {
+      rc = hipk_finalize_partials_strided(ctx, ctx->partials + (nb + L), gx, nsl, 1, nrm2_dev + res_slot);
+      if (rc) return rc;
+   }
+   return hipk_finalize_partials_strided(ctx, ctx->partials, gx, nsl, nsl, ov_dev);
+}
+
+extern "C" int hipk_ritz_update_overlaps(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const void *V, const void *W,
+      int64_t ldVW, int k, const double *h_dev, int ldh, const double *theta_dev, const hipk_job *jobs, int njobs,
+      double *nrm2_dev, int nbasis, const void *Q, int64_t ldQ, int L, double *ov_dev) {
+   DISPATCH_RT(dt, return ritz_ov_t<T>(ctx, m, (const T *)V, (const T *)W, ldVW, k, h_dev, ldh, theta_dev, jobs, njobs, nrm2_dev, nbasis, (const T *)Q, ldQ, L, ov_dev));
+}
+
+/* ============ fused Ritz residual + first-pass Gram-Schmidt overlaps (b = 1) ============
+ * r = W h - theta V h (written to dst), out = [ V' r | Q' r | r' r ] (+ [ W' r | W(:,k-1)' Q ]).
+ * In Generalized Davidson without preconditioner the residual IS the new basis vector, and
+ * the V and W rows needed for r are exactly the rows the first classical Gram-Schmidt pass
+ * would stream again for V' r (reference: Num_update_VWXR, auxiliary_eigs_normal.c:155-388,
+ * followed by Num_gemv_ddh in ortho.c:236-246).  Fusing them removes one full pass over V
+ * per outer iteration; the locked vectors Q are streamed here instead of in the dots launch.
+ *
+ * Column-split layout: the four waves of a workgroup walk the SAME rows (64*VW per step); wave w
+ * owns the basis columns [w*CPW, (w+1)*CPW) of V and W and the locked columns [w*QPW, (w+1)*QPW).
+ * Each wave forms its part of x = V h and y = W h, the parts meet in LDS (one barrier per step,
+ * double-buffered), every wave then knows r for its rows and accumulates the overlaps of ITS
+ * columns only.  A lane therefore holds 2*CPW + QPW loaded values and as many accumulators
+ * instead of 2k + L of each (206 VGPRs at k = 16, L = 16 in the one-lane-per-row form, i.e. two
+ * waves per SIMD): occupancy no longer falls with the basis size, every column is still read
+ * exactly once, and the W' r accumulators that make the projection column free
+ * cost CPW registers instead of k.
+ */
+struct HCol { double h[32]; };   /* the coefficient vector travels in the kernel arguments */
+
+template <typename T, int CPW, int QPW, int VW, bool WT>
+__global__ void __launch_bounds__(HIPK_BLOCK)
+ritz_cgs_kernel(const T *__restrict__ V, const T *__restrict__ W, int64_t ld, int k,
+      HCol hcol, double theta, const double *__restrict__ hdev, T *__restrict__ dst, const T *__restrict__ Q,
+      int64_t ldQ, int L, int64_t m, double *__restrict__ partials, int blocked, hipk_fin_args fa) {
+   typedef lanevec<T, VW> LV;
+   constexpr int QN = QPW > 0 ? QPW : 1;
+   __shared__ double sxy[2][2][VW][4][64];       /* [buffer][x|y][row in lane][wave][lane] */
+   __shared__ int s_last;
+   const int lane = threadIdx.x & 63;
+   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   const int j0 = wv * CPW, q0 = wv * QPW;
+   /* hdev != NULL: the coefficient vector and the Ritz value were left in HBM by hipk_rr_arrow (the iteration that was
+    * enqueued before the host had seen the previous one); a status other than 0 means there is no valid pair: nothing to do */
+   /* (no valid pair: nothing is streamed and nothing is written to dst, but the partial sums ARE stored — zeros — so that the
+    * second stage behind this launch, and whatever was enqueued behind that, work on defined numbers) */
+   bool dead = false;
+   if (hdev) {
+      dead = hdev[33] != 0.0;
+      theta = hdev[32];
+   }
+   double hj[CPW];
+   const T *vp[CPW], *wp[CPW], *qp[QN];
+#pragma unroll
+   for (int jj = 0; jj < CPW; jj++) {
+      const int j = j0 + jj;
+      hj[jj] = (j < k) ? (hdev ? hdev[j < 32 ? j : 0] : hcol.h[j < 32 ? j : 0]) : 0.0;
+      vp[jj] = V + (size_t)(j < k ? j : 0) * ld;
+      wp[jj] = W + (size_t)(j < k ? j : 0) * ld;
+   }
+#pragma unroll
+   for (int qq = 0; qq < QN; qq++) qp[qq] = (QPW > 0 && L > 0) ? Q + (size_t)(q0 + qq < L ? q0 + qq : 0) * ldQ : (const T *)V;
+   const T *wlast = W + (size_t)(k - 1) * ld;    /* newest W column, for W(:,k-1)' Q */
+   double ov[CPW], ow[WT ? CPW : 1], oq[QN], og[WT ? QN : 1], n2 = 0.0;
+#pragma unroll
+   for (int jj = 0; jj < CPW; jj++) ov[jj] = 0.0;
+#pragma unroll
+   for (int jj = 0; jj < (WT ? CPW : 1); jj++) ow[jj] = 0.0;
+#pragma unroll
+   for (int qq = 0; qq < QN; qq++) oq[qq] = 0.0;
+#pragma unroll
+   for (int qq = 0; qq < (WT ? QN : 1); qq++) og[qq] = 0.0;
+
+   const int64_t ngroups = m / (64 * VW);         /* full steps of 64*VW rows */
+   int buf = 0;
+   /* blocked: each workgroup walks one contiguous range of rows (sequential DRAM pages per column
+    * stream) instead of striding through the panel with the whole grid */
+   const int64_t gpb = (ngroups + gridDim.x - 1) / gridDim.x;
+   const int64_t gbeg = blocked ? (int64_t)blockIdx.x * gpb : blockIdx.x;
+   const int64_t gend = dead ? gbeg : (blocked ? (gbeg + gpb < ngroups ? gbeg + gpb : ngroups) : ngroups);
+   const int64_t gstep = blocked ? 1 : gridDim.x;
+   for (int64_t g = gbeg; g < gend; g += gstep, buf ^= 1) {
+      const int64_t e = g * 64 + lane;            /* index in LV units */
+      LV v[CPW], w[CPW], q[QN], wl;
+#pragma unroll
+      for (int jj = 0; jj < CPW; jj++)
+         if (j0 + jj < k) { v[jj] = ldstream<T, VW, 2>(vp[jj], e); w[jj] = ldstream<T, VW, 1>(wp[jj], e); }
+      if (QPW > 0) {
+#pragma unroll
+         for (int qq = 0; qq < QN; qq++)
+            if (q0 + qq < L) q[qq] = ldstream<T, VW, 2>(qp[qq], e);
+         if (WT && q0 < L) wl = ldstream<T, VW, 1>(wlast, e);
+      }
+      double px[VW], py[VW];
+#pragma unroll
+      for (int r = 0; r < VW; r++) { px[r] = 0.0; py[r] = 0.0; }
+#pragma unroll
+      for (int jj = 0; jj < CPW; jj++)
+         if (j0 + jj < k) {
+#pragma unroll
+            for (int r = 0; r < VW; r++) {
+               px[r] = fma((double)v[jj].e[r], hj[jj], px[r]);
+               py[r] = fma((double)w[jj].e[r], hj[jj], py[r]);
+            }
+         }
+#pragma unroll
+      for (int r = 0; r < VW; r++) { sxy[buf][0][r][wv][lane] = px[r]; sxy[buf][1][r][wv][lane] = py[r]; }
+      __syncthreads();
+      double rr[VW];
+      LV rt;
+#pragma unroll
+      for (int r = 0; r < VW; r++) {
+         const double x = (sxy[buf][0][r][0][lane] + sxy[buf][0][r][1][lane]) + (sxy[buf][0][r][2][lane] + sxy[buf][0][r][3][lane]);
+         const double y = (sxy[buf][1][r][0][lane] + sxy[buf][1][r][1][lane]) + (sxy[buf][1][r][2][lane] + sxy[buf][1][r][3][lane]);
+         rt.e[r] = (T)fma(-theta, x, y);
+         rr[r] = (double)rt.e[r];
+      }
+      if (wv == 0) {
+         ((LV *)dst)[e] = rt;
+#pragma unroll
+         for (int r = 0; r < VW; r++) n2 = fma(rr[r], rr[r], n2);
+      }
+#pragma unroll
+      for (int jj = 0; jj < CPW; jj++)
+         if (j0 + jj < k) {
+#pragma unroll
+            for (int r = 0; r < VW; r++) {
+               ov[jj] = fma((double)v[jj].e[r], rr[r], ov[jj]);
+               if (WT) ow[WT ? jj : 0] = fma((double)w[jj].e[r], rr[r], ow[WT ? jj : 0]);
+            }
+         }
+      if (QPW > 0) {
+#pragma unroll
+         for (int qq = 0; qq < QN; qq++)
+            if (q0 + qq < L) {
+#pragma unroll
+               for (int r = 0; r < VW; r++) {
+                  oq[qq] = fma((double)q[qq].e[r], rr[r], oq[qq]);
+                  if (WT) og[WT ? qq : 0] = fma((double)wl.e[r], (double)q[qq].e[r], og[WT ? qq : 0]);
+               }
+            }
+      }
+   }
+   /* Ragged tail (fewer than 64*VW rows): ONE more step of the same shape with element-wise guarded loads, done by
+    * the workgroup that has the fewest full steps (with the strided assignment the first one behind the remainder):
+    * as two one-row-per-lane steps on the last workgroup it was the tail of the whole launch -- 132.6 us against
+    * 122.6 us for 31 k more rows that divide evenly (k = 15, L = 10, m = 2 000 250). */
+   const int tailwg = blocked ? (int)gridDim.x - 1 : (int)(ngroups % gridDim.x);
+   if ((int)blockIdx.x == tailwg && ngroups * 64 * VW < m && !dead) {
+      const int64_t i0 = ngroups * 64 * VW + (int64_t)lane * VW;
+      double tv[CPW][VW], tw[CPW][VW], tq[QN][VW], twl[VW], px[VW], py[VW];
+      bool live[VW];
+#pragma unroll
+      for (int r = 0; r < VW; r++) { live[r] = i0 + r < m; px[r] = 0.0; py[r] = 0.0; twl[r] = 0.0; }
+#pragma unroll
+      for (int jj = 0; jj < CPW; jj++) {
+#pragma unroll
+         for (int r = 0; r < VW; r++) {
+            const bool on = live[r] && (j0 + jj < k);
+            tv[jj][r] = on ? (double)vp[jj][i0 + r] : 0.0;
+            tw[jj][r] = on ? (double)wp[jj][i0 + r] : 0.0;
+         }
+      }
+#pragma unroll
+      for (int qq = 0; qq < QN; qq++)
+#pragma unroll
+         for (int r = 0; r < VW; r++) tq[qq][r] = (QPW > 0 && live[r] && q0 + qq < L) ? (double)qp[qq][i0 + r] : 0.0;
+      if (WT && QPW > 0 && q0 < L) {
+#pragma unroll
+         for (int r = 0; r < VW; r++) twl[r] = live[r] ? (double)wlast[i0 + r] : 0.0;
+      }
+#pragma unroll
+      for (int jj = 0; jj < CPW; jj++)
+#pragma unroll
+         for (int r = 0; r < VW; r++) { px[r] = fma(tv[jj][r], hj[jj], px[r]); py[r] = fma(tw[jj][r], hj[jj], py[r]); }
+#pragma unroll
+      for (int r = 0; r < VW; r++) { sxy[buf][0][r][wv][lane] = px[r]; sxy[buf][1][r][wv][lane] = py[r]; }
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < VW; r++) {
+         const double x = (sxy[buf][0][r][0][lane] + sxy[buf][0][r][1][lane]) + (sxy[buf][0][r][2][lane] + sxy[buf][0][r][3][lane]);
+         const double y = (sxy[buf][1][r][0][lane] + sxy[buf][1][r][1][lane]) + (sxy[buf][1][r][2][lane] + sxy[buf][1][r][3][lane]);
+         const T rt = (T)fma(-theta, x, y);
+         const double rr = live[r] ? (double)rt : 0.0;
+         if (wv == 0 && live[r]) { dst[i0 + r] = rt; n2 = fma(rr, rr, n2); }
+#pragma unroll
+         for (int jj = 0; jj < CPW; jj++) {
+            ov[jj] = fma(tv[jj][r], rr, ov[jj]);
+            if (WT) ow[WT ? jj : 0] = fma(tw[jj][r], rr, ow[WT ? jj : 0]);
+         }
+#pragma unroll
+         for (int qq = 0; qq < QN; qq++) {
+            oq[qq] = fma(tq[qq][r], rr, oq[qq]);
+            if (WT) og[WT ? qq : 0] = fma(twl[r], tq[qq][r], og[WT ? qq : 0]);
+         }
+      }
+   }
+   /* every output belongs to exactly one wave: wave sums go straight to the block's partials, o-major
+    * (partials[o * nblocks + block]), o over [ V'r (k) | Q'r (L) | r'r | W'r (k) | W(:,k-1)'Q (L) ] */
+   const int nout = k + L + 1 + (WT ? k + L : 0);
+   const size_t nb = gridDim.x;
+   double *pcol = partials + blockIdx.x;
+#pragma unroll
+   for (int jj = 0; jj < CPW; jj++) {
+      const double t = hipk_wave_sum(ov[jj]);
+      if (lane == 0 && j0 + jj < k) hipk_pstore(fa, pcol + (size_t)(j0 + jj) * nb, t);
+      if (WT) {
+         const double u = hipk_wave_sum(ow[WT ? jj : 0]);
+         if (lane == 0 && j0 + jj < k) hipk_pstore(fa, pcol + (size_t)(k + L + 1 + j0 + jj) * nb, u);
+      }
+   }
+   if (QPW > 0) {
+#pragma unroll
+      for (int qq = 0; qq < QN; qq++) {
+         const double t = hipk_wave_sum(oq[qq]);
+         if (lane == 0 && q0 + qq < L) hipk_pstore(fa, pcol + (size_t)(k + q0 + qq) * nb, t);
+         if (WT) {
+            const double u = hipk_wave_sum(og[WT ? qq : 0]);
+            if (lane == 0 && q0 + qq < L) hipk_pstore(fa, pcol + (size_t)(2 * k + L + 1 + q0 + qq) * nb, u);
+         }
+      }
+   }
+   { const double t = hipk_wave_sum(n2); if (lane == 0 && wv == 0) hipk_pstore(fa, pcol + (size_t)(k + L) * nb, t); }
+   hipk_inkernel_finalize(partials, nout, gridDim.x, fa, &s_last);
+}
+
+static int rcgs_blocked(void) {               /* HIPK_RCGS_BLOCKED: measurement knob, read once */
+   static int v = -1;
+   if (v < 0) { const char *env = getenv("HIPK_RCGS_BLOCKED"); v = env ? atoi(env) : 0; }
+   return v;
+}
+
+template <typename T, int CPW, int VW, bool WT>
+static int ritz_cgs_q(hipk_ctx *ctx, int gx, const T *V, const T *W, int64_t ld, int k, const HCol &hcol,
+      double theta, const double *hdev, T *dst, const T *Q, int64_t ldQ, int L, int64_t m, const hipk_fin_args &fa) {
+   dim3 g(gx), b(HIPK_BLOCK);
+#define RCGS(QPWV) hipLaunchKernelGGL((ritz_cgs_kernel<T, CPW, QPWV, VW, WT>), g, b, 0, ctx->stream, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, ctx->partials, rcgs_blocked(), fa)
+   if (L == 0) RCGS(0);
+   else if (L <= 8) RCGS(2);
+   else if (L <= 16) RCGS(4);
+   else if (L <= 32) RCGS(8);
+   else return -1;
+#undef RCGS
+   HIPK_CHECK(hipGetLastError());
+   return 0;
+}
+
+template <typename T, int VW, bool WT>
+static int ritz_cgs_k(hipk_ctx *ctx, int gx, const T *V, const T *W, int64_t ld, int k, const HCol &hcol,
+      double theta, const double *hdev, T *dst, const T *Q, int64_t ldQ, int L, int64_t m, const hipk_fin_args &fa) {
+   if (k <= 8) return ritz_cgs_q<T, 2, VW, WT>(ctx, gx, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, fa);
+   if (k <= 16) return ritz_cgs_q<T, 4, VW, WT>(ctx, gx, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, fa);
+   if (k <= 24) return ritz_cgs_q<T, 6, VW, WT>(ctx, gx, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, fa);
+   return ritz_cgs_q<T, 8, VW, WT>(ctx, gx, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, fa);
+}
+
+template <typename T>
+static int ritz_cgs_t(hipk_ctx *ctx, int64_t m, const T *V, const T *W, int64_t ld, int k,
+      const double *hcol_host, double theta, const double *hdev, T *dst, const T *Q, int64_t ldQ, int L, int want_wtr, double *out_dev) {
+   if (k <= 0 || k > 32 || L < 0 || L > 32) return -1;
+   HCol hcol;
+   for (int j = 0; j < 32; j++) hcol.h[j] = (j < k && hcol_host) ? hcol_host[j] : 0.0;
+   constexpr int VWT = 2;   /* two rows per lane: 16-byte loads in double, 8-byte in float (register budget) */
+   const bool vec = aligned16(V, ld, sizeof(T)) && aligned16(W, ld, sizeof(T)) && aligned16(dst, ld, sizeof(T)) &&
+                    (L == 0 || aligned16(Q, ldQ, sizeof(T)));
+   const int rows_per_step = 64 * (vec ? VWT : 1);
+   static int bpc = -1;                        /* HIPK_RCGS_BPC: workgroups per CU (measurement knob, read once) */
+   if (bpc < 0) { const char *env = getenv("HIPK_RCGS_BPC"); bpc = env ? atoi(env) : 2; if (bpc < 1) bpc = 2; }
+   int gx = hipk_grid_for_rows(ctx, m, rows_per_step, bpc);
+   const int nout = k + L + 1 + (want_wtr ? k + L : 0);
+   if (hipk_reserve_partials(ctx, (size_t)gx * nout)) return -2;
+   const int pslot = hipk_prof_begin(HIPK_PROF_RITZ, ctx->stream, (double)m * sizeof(T) * (2.0 * k + L + 1));
+   int rc;
+   const hipk_fin_args fa = hipk_make_fin(ctx, out_dev, HIPK_FIN_RITZ, gx, nout);
+   if (vec) rc = want_wtr ? ritz_cgs_k<T, VWT, true>(ctx, gx, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, fa)
+                          : ritz_cgs_k<T, VWT, false>(ctx, gx, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, fa);
+   else rc = want_wtr ? ritz_cgs_k<T, 1, true>(ctx, gx, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, fa)
+                      : ritz_cgs_k<T, 1, false>(ctx, gx, V, W, ld, k, hcol, theta, hdev, dst, Q, ldQ, L, m, fa);
+   hipk_prof_end(pslot, ctx->stream);
+   if (rc) return rc;
+   if (fa.enabled) return 0;                    /* the last workgroup finalised */
+   return hipk_finalize_partials_t(ctx, ctx->partials, gx, nout, out_dev);
+}
+
+extern "C" int hipk_ritz_residual_overlaps(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const void *V,
+      const void *W, int64_t ldVW, int k, const double *hcol_host, double theta, void *dst,
+      const void *Q, int64_t ldQ, int L, int want_wtr, double *out_dev) {
+   hipk_note_turnaround(ctx);
+   DISPATCH_RT(dt, return ritz_cgs_t<T>(ctx, m, (const T *)V, (const T *)W, ldVW, k, hcol_host, theta, NULL, (T *)dst, (const T *)Q, ldQ, L, want_wtr, out_dev));
+}
+/* the same with the coefficient vector (hth_dev[0 .. k)), the Ritz value (hth_dev[32]) and a status word (hth_dev[33]) in HBM:
+ * the residual pass of an iteration enqueued before the host has seen the previous one (hipk_rr_arrow) */
+extern "C" int hipk_ritz_residual_overlaps_dev(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const void *V, const void *W, int64_t ldVW, int k,
+      const double *hth_dev, void *dst, const void *Q, int64_t ldQ, int L, int want_wtr, double *out_dev) {
+   if (!hth_dev) return -1;
+   DISPATCH_RT(dt, return ritz_cgs_t<T>(ctx, m, (const T *)V, (const T *)W, ldVW, k, NULL, 0.0, hth_dev, (T *)dst, (const T *)Q, ldQ, L, want_wtr, out_dev));
+}
+
+/* ---- Rayleigh-Ritz step of the pre-enqueued iteration: one eigenpair of the arrowhead matrix (primme_amd_kernels.h) ----
+ * One wave; lane j (< k) of every group of 16 lanes owns Ritz value j (all four groups compute the same, so every lane
+ * holds the sums).  Secular equation in the coordinate mu = lambda - theta_o of the nearer pole o:
+ *    g(mu) = (alpha - theta_o) - mu - sum_j z_j^2 / ((theta_j - theta_o) - mu),   strictly decreasing between two poles,
+ * safeguarded Newton (a step that leaves the bracket is replaced by its midpoint), until the step is below two ulps of mu. */
+/* sum over the 16 values a wave left in LDS (every lane gets the same bits: a fixed order) — no cross-lane traffic beyond
+ * two LDS round trips per Newton step */
+__device__ __forceinline__ double rr_sum16(const double *s) {
+   double a = 0.0;
+#pragma unroll
+   for (int i = 0; i < 16; i++) a += s[i];
+   return a;
+}
+/* what the Rayleigh-Ritz step keeps in LDS */
+struct RrShared { double sY[256], sG[160], sTh[16], sF[128], s_v[16], s_w[16], s_y[16]; };
+/* the step is run by ONE wave: as a launch of its own (a 64-thread workgroup: __syncthreads) or as the last part of the
+ * one-workgroup launch that finishes an iteration's tail (wave 0 of a wider workgroup: the LDS traffic of a single wave is
+ * ordered by itself, the fences keep the compiler from moving an access across the point) */
+struct RrSyncBlock { __device__ static __forceinline__ void sync() { __syncthreads(); } };
+struct RrSyncWave {
+   __device__ static __forceinline__ void sync() {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+   }
+};
+/* lane = 0..63 of the one wave.  rr_arrow_stage: the step's inputs into LDS — independent of |t|^2 and t'At, so the launch that
+ * first has to add those up issues these loads before it does; rr_arrow_solve: the step itself, n2 = |t|^2 and alpha = t'At of
+ * the iteration whose reductions are in fov[0 .. nfov) */
+__device__ __forceinline__ void rr_arrow_stage(const hipk_rr_in &in, const double *__restrict__ fov, int nfov, RrShared &S, const int lane) {
+   /* The kernel arguments live in host-visible memory on this stack: indexed, per-lane reads of `in` would each be a trip over
+    * PCIe (the first version of this kernel did that in its loops and took longer than the host round trip it replaces).
+    * Everything is brought into LDS with ONE batch of loads — the arguments and this iteration's reductions together. */
+   const int j = lane & 15;
+   double ty[4], tg[3], tf[2];
+#pragma unroll
+   for (int u = 0; u < 4; u++) ty[u] = in.Y[lane + 64 * u];
+#pragma unroll
+   for (int u = 0; u < 3; u++) tg[u] = (lane + 64 * u < 160) ? in.G[lane + 64 * u] : 0.0;
+   const double tt = in.theta[j];
+#pragma unroll
+   for (int u = 0; u < 2; u++) tf[u] = (lane + 64 * u < nfov) ? fov[lane + 64 * u] : 0.0;
+#pragma unroll
+   for (int u = 0; u < 4; u++) S.sY[lane + 64 * u] = ty[u];
+#pragma unroll
+   for (int u = 0; u < 3; u++) if (lane + 64 * u < 160) S.sG[lane + 64 * u] = tg[u];
+   if (lane < 16) S.sTh[lane] = tt;
+#pragma unroll
+   for (int u = 0; u < 2; u++) S.sF[lane + 64 * u] = tf[u];
+}
+template <class SY>
+__device__ __forceinline__ void rr_arrow_solve(const hipk_rr_in &in, int nfov, double n2, double alpha,
+      RrShared &S, double *__restrict__ out, double *__restrict__ out_host, const int lane) {
+   double *sY = S.sY, *sG = S.sG, *sTh = S.sTh, *sF = S.sF, *s_v = S.s_v, *s_w = S.s_w, *s_y = S.s_y;
+   const int j = lane & 15, k = in.k, L = in.L;
+   const bool on = lane < 16 && j < k;
+   SY::sync();
+   const double sgn = in.largest ? -1.0 : 1.0;
+   const double nt = sqrt(n2);
+   const double cv = on ? sF[j] : 0.0;                        /* V'r */
+   const double wr = on ? sF[k + L + 1 + j] : 0.0;            /* W'r */
+   double gq = 0.0;                                           /* (G Q'r)_j */
+   for (int l = 0; l < L; l++) {
+      const double g = (in.grow_row && j == k - 1) ? sF[2 * k + L + 1 + l] : sG[j + l * k];
+      gq = on ? fma(g, sF[k + l], gq) : 0.0;
+   }
+   /* z_i = (Y(:,i)'(W'r - G Q'r) - theta_i Y(:,i)'(V'r)) / |t| */
+   SY::sync();
+   if (lane < 16) { s_v[lane] = on ? wr - gq : 0.0; s_w[lane] = cv; }
+   SY::sync();
+   double a1 = 0.0, a2 = 0.0;
+   for (int r = 0; r < k; r++) { const double yv = sY[r + j * k]; a1 = fma(yv, s_v[r], a1); a2 = fma(yv, s_w[r], a2); }
+   const double thj = on ? sTh[j] : 0.0;
+   const double z = on ? sgn * (a1 - thj * a2) / nt : 0.0;     /* the negated problem for `largest`: -M = [-Theta -z; -z' -alpha] */
+   const double th = sgn * thj, al = sgn * alpha;               /* ascending in j for both targets */
+   const double z2 = z * z;
+   const int c = in.cand;
+   int status = (k < 1 || k > 16 || L < 0 || L > 10 || c < 0 || c > k || nfov > 126 || !(n2 > 0.0)) ? 1 : 0;
+   SY::sync();
+   if (lane < 16) { s_v[lane] = on ? th : 0.0; s_w[lane] = z2; }
+   SY::sync();
+   /* poles strictly increasing, everything finite (every lane looks at all of them: uniform control flow) */
+   double zn2 = 0.0;
+   for (int i = 0; i < k; i++) {
+      const double ti = s_v[i], zi = s_w[i];
+      if (!(isfinite(ti) && isfinite(zi)) || (i + 1 < k && !(ti < s_v[i + 1]))) status = status ? status : 2;
+      zn2 += zi;
+   }
+   if (!isfinite(al)) status = status ? status : 2;
+   const double zn = sqrt(zn2);
+   double lam = 0.0, yj = 0.0, ynorm2 = 1.0;
+   if (status == 0) {
+      const double th0 = s_v[0], thl = s_v[k - 1];
+      const double thc = s_v[c < k ? c : k - 1], thcm = s_v[c > 0 ? c - 1 : 0];
+      int o;
+      double lo, hi;
+      if (c == 0) { o = 0; lo = fmin(0.0, al - th0) - zn - 1e-300; lo -= 4e-16 * fabs(lo); hi = 0.0; }
+      else if (c == k) { o = k - 1; lo = 0.0; hi = fmax(0.0, al - thl) + zn + 1e-300; hi += 4e-16 * fabs(hi); }
+      else {
+         /* the sign of g at the middle of the interval says which pole the root is closer to */
+         const double mid = 0.5 * (thc - thcm);
+         double sm = 0.0;
+         for (int i = 0; i < k; i++) sm += s_w[i] / ((s_v[i] - thcm) - mid);
+         const double gm = (al - thcm) - mid - sm;
+         if (gm > 0.0) { o = c; lo = -mid; hi = 0.0; }
+         else { o = c - 1; lo = 0.0; hi = mid; }
+      }
+      const double tho = s_v[o];
+      const double dj = th - tho, a0 = al - tho;
+      const bool neg = hi == 0.0;                               /* the root lies below its pole (mu < 0) or above it (mu > 0) */
+      const double B = s_w[o];                                  /* z_o^2: the pole's weight */
+      const bool mine = on && j != o;
+      double mu = 0.5 * (lo + hi);
+      int it = 0;
+      /* The pole at the origin is kept EXACT and the rest of the sum is replaced by its tangent at the current point
+       * (what LAPACK's dlaed4 does with two poles): g(mu) ~ (a0 - S + S' mu_i) - (1 + S') mu + z_o^2 / mu, a quadratic in mu
+       * whose root on the bracket's side of the pole is the next point.  Converges in 3-5 steps where Newton on g itself
+       * crawls (the root of the wanted pair sits within 1e-8 of its pole: the first version of this loop averaged 55 steps,
+       * 19 us per launch).  Safeguard: a point outside the bracket is replaced by its midpoint. */
+      for (; it < 100; it++) {
+         const double r = 1.0 / (dj - mu);
+         const double t = mine ? z2 * r : 0.0;
+         SY::sync();
+         if (lane < 16) { s_y[lane] = t; sF[lane] = mine ? t * r : 0.0; }
+         SY::sync();
+         const double S = rr_sum16(s_y), Sp = rr_sum16(sF);
+         const double pole = B / mu, g = a0 - mu - S + pole;
+         if (!(g == g)) { status = 3; break; }
+         /* converged: g is zero to the rounding of its own terms (going on from here only moves mu by an ulp — or throws the
+          * next point an ulp outside the bracket, whose far end was never tightened, and the midpoint fall-back then crawls) */
+         if (fabs(g) <= 2.3e-16 * (fabs(a0) + fabs(mu) + fabs(S) + fabs(pole))) break;
+         if (g > 0.0) lo = mu; else hi = mu;
+         const double A = 1.0 + Sp, Cc = a0 - S + Sp * mu, disc = sqrt(Cc * Cc + 4.0 * A * B);
+         double mn;
+         if (neg) mn = (Cc > 0.0) ? -2.0 * B / (Cc + disc) : (Cc - disc) / (2.0 * A);
+         else mn = (Cc < 0.0) ? 2.0 * B / (disc - Cc) : (Cc + disc) / (2.0 * A);
+         if (!(mn > lo && mn < hi)) { if (fabs(mn - mu) <= 1e-14 * fabs(mu)) break; mn = 0.5 * (lo + hi); }
+         const double step = fabs(mn - mu);
+         const bool done = step <= 4.4e-16 * fabs(mn) || mn == lo || mn == hi;
+         mu = mn;
+         if (done) break;
+      }
+      if (it >= 100) status = 4;
+      lam = sgn * (tho + mu);
+      yj = on ? z / (mu - dj) : 0.0;                              /* eigenvector [y; 1] of the (possibly negated) arrowhead */
+      SY::sync();
+      if (lane < 16) s_y[lane] = yj * yj;
+      SY::sync();
+      ynorm2 = 1.0 + rr_sum16(s_y);
+      if (!isfinite(lam) || !isfinite(ynorm2)) status = 5;
+   }
+   /* back to the basis [V t]: h = [Y y; 1] / |[y; 1]| */
+   const double inv = 1.0 / sqrt(ynorm2);
+   SY::sync();
+   if (lane < 16) s_y[lane] = yj;
+   SY::sync();
+   double hv = 0.0;
+   for (int i = 0; i < k; i++) hv = fma(sY[j + i * k], s_y[i], hv);
+   hv *= inv;
+   if (lane < 16) {
+      if (on) { out[j] = hv; if (out_host) out_host[j] = hv; }
+      if (lane == 0) {
+         out[k] = inv; out[32] = lam; out[33] = (double)status;
+         if (out_host) { out_host[k] = inv; out_host[32] = lam; out_host[33] = (double)status; }
+      }
+   }
+}
+
+__global__ void __launch_bounds__(64)
+rr_arrow_kernel(hipk_rr_in in, const double *__restrict__ fov, int nfov, const double *__restrict__ alpha_dev,
+      double *__restrict__ out, double *__restrict__ out_host) {
+   __shared__ RrShared S;
+   const double n2 = fov[nfov], alpha = alpha_dev[0];
+   rr_arrow_stage(in, fov, nfov, S, (int)threadIdx.x);
+   rr_arrow_solve<RrSyncBlock>(in, nfov, n2, alpha, S, out, out_host, (int)threadIdx.x);
+   /* no completion flag of its own: the host looks at the pinned copy after the flagged second stage of the residual pass that
+    * follows in the stream (a kernel boundary on the queue lies in between) */
+}
+extern "C" int hipk_rr_arrow(hipk_ctx *ctx, const hipk_rr_in *in, const double *fov_dev, int nfov, const double *alpha_dev, double *out_dev) {
+   if (!in || in->k < 1 || in->k > 16 || in->L < 0 || in->L > 10) return -1;
+   if (nfov > 126) return -1;
+   hipLaunchKernelGGL(rr_arrow_kernel, dim3(1), dim3(64), 0, ctx->stream, *in, fov_dev, nfov, alpha_dev, out_dev, hipk_mirror_of(ctx, out_dev));
+   HIPK_CHECK(hipGetLastError());
+   return 0;
+}
+
+/* ---- the ONE small launch that finishes the tail of a block-size-1 iteration (hipk_tail_defer / hipk_tail_finish) ----
+ * np2 partial sums of |t|^2 (left by the Gram-Schmidt update; already added up, in the same order, by every workgroup of the
+ * operator launch that normalised with them) and np3 partial sums of t'At (left by that operator launch) -> their sums in HBM
+ * and in the pinned mirror; row-partitioned runs on the peer-to-peer transport exchange t'At with the other ranks here; then —
+ * when the next iteration is enqueued behind this one — the Rayleigh-Ritz step of that iteration (rr_arrow_body: what
+ * rr_arrow_kernel does as a launch of its own), and the completion flag last.  Replaces two second-stage launches and the
+ * one-wave launch: three kernel boundaries and ~10 us less per outer iteration. */
+template <bool XR>
+__global__ void __launch_bounds__(FIN_TAIL_MAXBLOCK)
+tail_finish_kernel(const double *__restrict__ p2, int np2, const double *__restrict__ p3, int np3, double *__restrict__ norm2_out,
+      double *__restrict__ norm2_host, double *__restrict__ dot_out, double *__restrict__ dot_host, hipk_fin_flag fin, hipk_xr_dev xr,
+      int do_rr, hipk_rr_in in, const double *__restrict__ fov, int nfov, double *__restrict__ rr_out, double *__restrict__ rr_host) {
+   __shared__ double sm2[4], sm3[FIN_TAIL_MAXBLOCK / HIPK_WAVE];
+   __shared__ RrShared S;
+   /* the Rayleigh-Ritz step's inputs (3.4 KB of kernel arguments + this iteration's overlaps) do not depend on the two sums:
+    * wave 0 has them on their way before anybody adds anything */
+   if (do_rr && threadIdx.x < 64) rr_arrow_stage(in, fov, nfov, S, (int)threadIdx.x);
+   if (np2 > 0) hipk_block_sum256_put(p2, np2, sm2);
+   {  /* t'At: the order of hipk_finalize_kernel (one output) at the same workgroup size — the bits of the separate launch */
+      const int nt = blockDim.x;
+      double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+      int b = threadIdx.x;
+      for (; b + 3 * nt < np3; b += 4 * nt) {
+         const double a0 = p3[b], a1 = p3[b + nt], a2 = p3[b + 2 * nt], a3 = p3[b + 3 * nt];
+         s0 += a0; s1 += a1; s2 += a2; s3 += a3;
+      }
+      {
+         const int last = np3 - 1;
+         const int b0 = b, b1 = b + nt, b2 = b + 2 * nt;
+         const double a0 = p3[b0 < last ? b0 : last], a1 = p3[b1 < last ? b1 : last], a2 = p3[b2 < last ? b2 : last];
+         s0 += b0 < np3 ? a0 : 0.0; s1 += b1 < np3 ? a1 : 0.0; s2 += b2 < np3 ? a2 : 0.0;
+      }
+      const double s = hipk_wave_sum((s0 + s1) + (s2 + s3));
+      if ((threadIdx.x & 63) == 0) sm3[threadIdx.x >> 6] = s;
+   }
+   __syncthreads();
+   if (threadIdx.x >= 64) return;
+   double v3 = 0.0;
+   {
+      const int nw = blockDim.x >> 6;
+      for (int w = 0; w < nw; w++) v3 += sm3[w];
+   }
+   const double v2 = np2 > 0 ? hipk_block_sum256_get(sm2) : 0.0;
+   if (XR) v3 = hipk_xr_exchange(xr, 0u, v3, threadIdx.x < 16);
+   if (threadIdx.x == 0) {
+      dot_out[0] = v3;
+      if (dot_host) dot_host[0] = v3;
+      if (np2 > 0) { norm2_out[0] = v2; if (norm2_host) norm2_host[0] = v2; }
+   }
+   if (do_rr) rr_arrow_solve<RrSyncWave>(in, nfov, np2 > 0 ? v2 : fov[nfov], v3, S, rr_out, rr_host, (int)threadIdx.x);
+   /* one workgroup: no ticket — the mirrored results are out (system scope) before the flag */
+   if (threadIdx.x == 0 && fin.flag) {
+      __threadfence_system();
+      *(volatile unsigned long long *)fin.flag = fin.seq;
+   }
+}
+
+extern "C" int hipk_tail_finish(hipk_ctx *ctx, const hipk_rr_in *in, const double *fov_dev, int nfov, const double *alpha_dev, double *hnext_out) {
+   const int np2 = ctx->tail_np2, np3 = ctx->tail_np3;
+   double *n2o = ctx->tail_norm2_out, *doto = ctx->tail_dot_out;
+   hipk_tail_abandon(ctx);
+   if (in && (in->k < 1 || in->k > 16 || in->L < 0 || in->L > 10 || nfov > 126 || !hnext_out)) return -1;
+   if (np3 <= 0) {
+      /* t'At was not deferred (another operator path, the CPU checker): finish |t|^2 if it is still waiting, then the
+       * Rayleigh-Ritz step as a launch of its own */
+      if (np2 > 0) { const int rc = hipk_finalize_partials_t(ctx, ctx->tailp, np2, 1, n2o); if (rc) return rc; }
+      if (in) return hipk_rr_arrow(ctx, in, fov_dev, nfov, alpha_dev, hnext_out);
+      return 0;
+   }
+   if (in && (alpha_dev != doto || (np2 > 0 && fov_dev + nfov != n2o))) return -1;
+   const hipk_xr_dev xr = hipk_xr_take(ctx, doto, 1);
+   if (xr.tab && np2 > 0) return -1;            /* |t|^2 of a row-partitioned run must be global before the operator launch */
+   const hipk_fin_flag ff = hipk_next_flag(ctx, doto);
+   const int nt = np3 <= 1024 ? HIPK_BLOCK : (np3 <= 2048 ? 512 : FIN_TAIL_MAXBLOCK);      /* = fin_block_for (hipk_core.hip) */
+   hipk_rr_in none;
+   if (!in) memset(&none, 0, sizeof(none));
+   if (xr.tab)
+      hipLaunchKernelGGL((tail_finish_kernel<true>), dim3(1), dim3(nt), 0, ctx->stream, ctx->tailp, np2, ctx->partials, np3, n2o, np2 > 0 ? hipk_mirror_of(ctx, n2o) : NULL,
+            doto, hipk_mirror_of(ctx, doto), ff, xr, in ? 1 : 0, in ? *in : none, fov_dev, nfov, hnext_out, in ? hipk_mirror_of(ctx, hnext_out) : NULL);
+   else
+      hipLaunchKernelGGL((tail_finish_kernel<false>), dim3(1), dim3(nt), 0, ctx->stream, ctx->tailp, np2, ctx->partials, np3, n2o, np2 > 0 ? hipk_mirror_of(ctx, n2o) : NULL,
+            doto, hipk_mirror_of(ctx, doto), ff, xr, in ? 1 : 0, in ? *in : none, fov_dev, nfov, hnext_out, in ? hipk_mirror_of(ctx, hnext_out) : NULL);
+   HIPK_CHECK(hipGetLastError());
+   return 0;
+}

@@ -530,10 +530,6 @@ jacobi_kernel(const T *__restrict__ diag, JacShift sh, double min_den, const T *
    }
 }
 
-static size_t elem_size(hipk_dtype dt) {
-   return dt == HIPK_F64 ? 8 : dt == HIPK_F32 ? 4 : dt == HIPK_C64 ? 16 : 8;
-}
-
 static int csr_create_impl(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local,
       int64_t ncols_global, int64_t row0, int64_t x0, int64_t xlen, const int32_t *rowptr_host,
       const int32_t *colind_host, const void *values_host, hipk_csr **out) {
@@ -546,7 +542,7 @@ static int csr_create_impl(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local,
    A->x0 = x0; A->xlen = xlen;
    const int64_t nnz = rowptr_host[nrows_local];
    A->nnz = nnz;
-   const size_t es = elem_size(dt);
+   const size_t es = hipk_elem_size(dt);
 
    /* tiles + halo extent + diagonal on the host (one pass) */
    std::vector<int32_t> tiles;
@@ -701,7 +697,7 @@ extern "C" int hipk_stencil_create(hipk_ctx *ctx, hipk_dtype dt, int nx, int ny,
    const int64_t above = n - (row0 + nrows_local);
    A->halo_hi = above > 0 ? (reach < above ? reach : above) : 0;
    A->ld_lo = A->halo_lo; A->ld_hi = A->halo_hi;
-   const size_t es = elem_size(dt);
+   const size_t es = hipk_elem_size(dt);
    if (hipk_malloc(ctx, (size_t)nrows_local * es, &A->diag)) return -2;
    int gx = hipk_grid_for_rows(ctx, nrows_local, HIPK_BLOCK * 4, 8);
    if (dt == HIPK_F64)
@@ -999,7 +995,7 @@ extern "C" int hipk_jacobi_apply(void *hip_stream, hipk_dtype dt, int64_t m, con
    if (ncols <= 0) return 0;
    if (!(min_den > 0.0)) min_den = 1e-300;
    if (ncols > 64) return -1;
-   hipk_prof_scope ps_(HIPK_PROF_VEC, (hipStream_t)hip_stream, (double)m * (double)elem_size(dt) * (2.0 * ncols) + (double)m * (double)elem_size(hipk_real_of(dt)));
+   hipk_prof_scope ps_(HIPK_PROF_VEC, (hipStream_t)hip_stream, (double)m * (double)hipk_elem_size(dt) * (2.0 * ncols) + (double)m * (double)hipk_elem_size(hipk_real_of(dt)));
    if (HIPK_IS_Z(dt)) {
       int dev = 0, ncu = 256;
       if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
