@@ -237,6 +237,28 @@ void primme_amd_mass_matvec(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy, 
  * createInvDiagPrecNative / examples/ex_eigs_dseq.c:187-202). */
 void primme_amd_jacobi_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
       int *blockSize, struct primme_params *primme, int *ierr);
+/* Chebyshev polynomial preconditioner y = p(A) x: the `steps`-th iterate of Chebyshev iteration for (A - sigma I) y = x
+ * started from y = 0, which damps the part [lo, hi] of the spectrum (steps - 1 applications of the operator per vector; no
+ * reference counterpart).  primme->preconditioner = the operator handle, configured with
+ *    primme_amd_operator_set_chebyshev(op, steps, lo, hi, fixed, shift)
+ * fixed = 1: sigma = shift, which must not lie inside (lo, hi).  fixed = 0: column c uses primme->ShiftsForPreconditioner[c],
+ * kept at or below lo for primme_smallest and at or above hi for primme_largest; any other target makes the callback set
+ * *ierr = 1.  hi = NaN: the Gershgorin upper bound of the operator (primme_amd_operator_gershgorin; collective when the
+ * operator is row-partitioned).  Returns -1 for steps < 1, lo = NaN, lo >= hi or a fixed shift inside the interval.
+ * lo is the upper end of what is WANTED (for the smallest eigenvalues: anything in the gap above them, e.g. a Ritz value
+ * of a coarse run).  hi must bound the spectrum: p grows without limit on (hi, lambda_max], the preconditioner is then bad
+ * (nothing faults).  Block columns beyond 8 are processed in chunks; the operator owns the scratch panels.
+ * PRIMME_AMD_CHEB_UNFUSED=1 (read by primme_amd_operator_set_chebyshev) keeps the operator product and the recurrence in
+ * separate launches for every operator (A/B measurements); by default single-rank real CSR operators run both in one pass.
+ * The applications of the operator inside the preconditioner are not counted in stats.numMatvecs (the reference does not
+ * count work inside a user preconditioner either); primme_amd_chebyshev_stats returns, for this process since the last
+ * call, the vectors preconditioned, the operator products (vectors) spent on them and how many of those ran fused. */
+struct primme_amd_operator;
+int primme_amd_operator_set_chebyshev(struct primme_amd_operator *op, int steps, double lo, double hi, int fixed, double shift);
+int primme_amd_operator_gershgorin(struct primme_amd_operator *op, double *lo, double *hi);
+void primme_amd_chebyshev_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
+      int *blockSize, struct primme_params *primme, int *ierr);
+void primme_amd_chebyshev_stats(long *applies, long *operator_products, long *fused_steps);
 /* globalSumReal over RCCL: set primme->commInfo = handle from primme_amd_comm_create().
  * When the solver sees this exact function installed it reduces its DEVICE partials
  * with ncclAllReduce before the (single) device->host copy; called directly it also

@@ -387,6 +387,29 @@ int hipk_jacobi_apply(void *hip_stream, hipk_dtype dt, int64_t m, const void *di
 hipk_dtype hipk_csr_dtype(const hipk_csr *A);
 int64_t hipk_csr_nrows(const hipk_csr *A);
 
+/* ---- Chebyshev polynomial preconditioner (csrc/hipk_cheb.hip; no reference counterpart) -------------------------
+ * One step of the three-term recurrence is a linear combination per row with REAL coefficients per column c,
+ *    Out(:,c) = cy[c] Yk(:,c) + cp[c] Yprev(:,c) + cx[c] X(:,c) + cw[c] (A Yk)(:,c)
+ * (the shift of A - sigma I is folded into cy; primme_amd_chebyshev_precond computes the coefficients on the host in
+ * double).  At most HIPK_CHEB_MAXCOLS columns per launch.
+ *   hipk_cheb_update: the combination with the product already in W (W, Yk, Yprev may each be NULL: that term is left
+ *     out); one pass with 16-byte accesses when every panel is 16-byte aligned; row-local, so Out may be one of the
+ *     inputs (the recurrence writes y_{k+1} over y_{k-1}); all four dtypes.
+ *   hipk_csr_cheb_step: product and combination in ONE pass over the matrix (Yprev may be NULL; Out must not be Yk, which
+ *     other rows gather from; Out may be Yprev); returns 1 when the operator has no fused form (anything but a real
+ *     single-rank CSR matrix without halo, in its row-pattern or row-tile form): the caller then runs the operator and
+ *     hipk_cheb_update.
+ *   hipk_csr_gershgorin: out[0] = min_i (a_ii - sum_{j != i} |a_ij|), out[1] = max_i (a_ii + sum_{j != i} |a_ij|) over
+ *     the LOCAL rows, one pass over the matrix on the device (the stencil form answers analytically); complete on
+ *     return.  An empty slab gives [+inf, -inf]. */
+#define HIPK_CHEB_MAXCOLS 8
+typedef struct hipk_cheb_coef { double cy[HIPK_CHEB_MAXCOLS], cp[HIPK_CHEB_MAXCOLS], cx[HIPK_CHEB_MAXCOLS], cw[HIPK_CHEB_MAXCOLS]; } hipk_cheb_coef;
+int hipk_cheb_update(void *hip_stream, hipk_dtype dt, int64_t m, int nx, const hipk_cheb_coef *coef, const void *X, int64_t ldx,
+      const void *W, int64_t ldw, const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp, void *Out, int64_t ldo);
+int hipk_csr_cheb_step(hipk_csr *A, void *hip_stream, int nx, const hipk_cheb_coef *coef, const void *X, int64_t ldx,
+      const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp, void *Out, int64_t ldo);
+int hipk_csr_gershgorin(hipk_csr *A, void *hip_stream, double out[2]);
+
 /* ---- Rayleigh-Ritz small solve on the device (reference solve_projection.c:188-331 calls xHEEVX,
  * blaslapack.c:1024-1143).  Symmetric n x n (n <= 64), upper triangle of A_host referenced;
  * eigenvalues ascending in evals_host, orthonormal eigenvectors in Z_host.  One workgroup, parallel

@@ -158,6 +158,11 @@ class HipkRrIn(C.Structure):
                 ("theta", C.c_double * 16), ("Y", C.c_double * 256), ("G", C.c_double * 160)]
 
 
+class HipkChebCoef(C.Structure):
+    """include/primme_amd_kernels.h: hipk_cheb_coef (per-column coefficients of one Chebyshev step, at most 8 columns)"""
+    _fields_ = [("cy", C.c_double * 8), ("cp", C.c_double * 8), ("cx", C.c_double * 8), ("cw", C.c_double * 8)]
+
+
 # PRIMME_AMD_LIB: another build of the product library (measurement only: the build-time variants of scripts/build_variant.sh)
 PRODUCT_LIB = os.environ.get("PRIMME_AMD_LIB") or os.path.join(_HERE, "libprimme_amd.so")
 
@@ -268,6 +273,24 @@ def declare_kernels(lib):
         lib.primme_amd_comm_destroy.argtypes = [_vp]
 
 
+def declare_chebyshev(lib):
+    """The Chebyshev preconditioner's entry points: product library only (load_product).  Not part of declare_kernels,
+    which oracle/checkers.py also applies to the CPU checker build, and that has no such symbols."""
+    P = C.POINTER
+    lib.primme_amd_operator_set_chebyshev.argtypes = [_vp, _i, C.c_double, C.c_double, _i, C.c_double]
+    lib.primme_amd_operator_set_chebyshev.restype = C.c_int
+    lib.primme_amd_operator_gershgorin.argtypes = [_vp, _dp, _dp]
+    lib.primme_amd_operator_gershgorin.restype = C.c_int
+    lib.primme_amd_chebyshev_stats.argtypes = [P(C.c_long), P(C.c_long), P(C.c_long)]
+    lib.primme_amd_chebyshev_stats.restype = None
+    lib.hipk_cheb_update.argtypes = [_vp, _i, _i64, _i, P(HipkChebCoef), _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]
+    lib.hipk_cheb_update.restype = C.c_int
+    lib.hipk_csr_cheb_step.argtypes = [_vp, _vp, _i, P(HipkChebCoef), _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]
+    lib.hipk_csr_cheb_step.restype = C.c_int
+    lib.hipk_csr_gershgorin.argtypes = [_vp, _vp, _dp]
+    lib.hipk_csr_gershgorin.restype = C.c_int
+
+
 _cache = {}
 
 
@@ -287,5 +310,6 @@ def load_product():
         lib = C.CDLL(PRODUCT_LIB)
         declare_solver(lib, "hip_")
         declare_kernels(lib)
+        declare_chebyshev(lib)
         _cache["product"] = lib
     return _cache["product"]

@@ -55,6 +55,8 @@ class Result:
         self.params = {k: getattr(params, k) for k in ("maxBasisSize", "minRestartSize", "maxBlockSize",
                                                        "locking", "orth", "aNorm", "eps", "initSize", "dynamicMethodSwitch")}
         self.params["maxPrevRetain"] = params.restartingParams.maxPrevRetain
+        # Chebyshev preconditioner only: {"applies", "operator_products", "fused_steps"} of this solve (counted in vectors)
+        self.precond_stats = None
 
 
 class HipBackend:
@@ -181,6 +183,15 @@ class Session:
               constraints=None, user_precond=None, tweak=None):
         lib, op, dtype = self.lib, self.op, self.dtype
         keep = []
+        cheb = isinstance(precond, (tuple, list)) and len(precond) > 0 and precond[0] == "chebyshev"
+        if cheb:
+            if not 3 <= len(precond) <= 5:
+                raise ValueError("precond: ('chebyshev', steps, lo[, hi[, shift]])")
+            if not (self.be.native_operator and hasattr(lib, "primme_amd_chebyshev_precond")):
+                raise ValueError(f"precond={precond!r}: the Chebyshev preconditioner applies the device operator of the product "
+                                 f"library; back end {self.backend!r} has no such operator")
+            if user_precond is not None:
+                raise ValueError("precond=('chebyshev', ...) and user_precond exclude each other")
         p = F.PrimmeParams()
         nLocal = op.nrows
         v0 = None if v0 is None else np.asarray(v0, dtype=dtype).reshape(nLocal, -1)
@@ -242,6 +253,18 @@ class Session:
             if user_precond is not None:     # an application preconditioner callback (same pointer conventions as the matvec)
                 keep.append(user_precond)
                 p.applyPreconditioner = C.cast(user_precond, C.c_void_p)
+                p.correctionParams.precondition = 1
+            elif cheb:
+                # ("chebyshev", steps, lo[, hi]): the solver's shifts; ("chebyshev", steps, lo, hi, shift): fixed shift.
+                # hi left out (or None): the Gershgorin upper bound of the operator
+                steps, lo = int(precond[1]), float(precond[2])
+                hi = float("nan") if len(precond) < 4 or precond[3] is None else float(precond[3])
+                fixed = len(precond) == 5
+                if lib.primme_amd_operator_set_chebyshev(self.oph, steps, lo, hi, int(fixed), float(precond[4]) if fixed else 0.0):
+                    raise ValueError(f"precond={precond!r}: needs steps >= 1, lo < hi and a fixed shift outside (lo, hi)")
+                lib.primme_amd_chebyshev_stats(None, None, None)      # the counters are per process: start this solve at zero
+                p.preconditioner = self.oph
+                p.applyPreconditioner = C.cast(lib.primme_amd_chebyshev_precond, C.c_void_p)
                 p.correctionParams.precondition = 1
             elif precond is not None:
                 # "jacobi": per-vector shifts of the solver; ("jacobi", s): fixed K = diag(A) - s
@@ -308,7 +331,12 @@ class Session:
             import torch
             torch.cuda.synchronize()
             evecs = evecs_t.cpu().numpy() if return_evecs else None
-        return Result(ret, evals, None if evecs is None else evecs[nOC:nOC + numEvals].T.copy(), resNorms, p)
+        res = Result(ret, evals, None if evecs is None else evecs[nOC:nOC + numEvals].T.copy(), resNorms, p)
+        if cheb:
+            st = [C.c_long(0), C.c_long(0), C.c_long(0)]
+            lib.primme_amd_chebyshev_stats(*[C.byref(v) for v in st])
+            res.precond_stats = dict(zip(("applies", "operator_products", "fused_steps"), (v.value for v in st)))
+        return res
 
 
 def eigsh(op, backend="hip", comm=None, dtype=np.float64, complex_form="native", mass=None, **kw):
@@ -316,7 +344,9 @@ def eigsh(op, backend="hip", comm=None, dtype=np.float64, complex_form="native",
 
     v0: optional (nLocal x initSize) initial guesses -> initBasisMode defaults to
     primme_init_user so that no random numbers enter (parity runs).
-    precond: None | "jacobi" (Davidson: per-vector shifts) | ("jacobi", shift) (fixed shift).
+    precond: None | "jacobi" (Davidson: per-vector shifts) | ("jacobi", shift) (fixed shift) |
+    ("chebyshev", steps, lo[, hi]) (polynomial preconditioner with the solver's shifts; hi defaults to the Gershgorin
+    bound) | ("chebyshev", steps, lo, hi, shift) (fixed shift).  Result.precond_stats then holds its counters.
     """
     s = Session(op, comm=comm, dtype=dtype, backend=backend, complex_form=complex_form, mass=mass)
     try:

@@ -24,6 +24,13 @@ struct primme_amd_operator {
    double jacobi_shift;
    int ldscale;              /* 2 when A is the real-equivalent form of a Hermitian matrix and the
                                 callbacks are handed leading dimensions in complex elements */
+   /* Chebyshev polynomial preconditioner (primme_amd_chebyshev_precond): steps = 0 until configured */
+   int cheb_steps, cheb_fixed, cheb_unfused, cheb_fused_all;
+   double cheb_lo, cheb_hi, cheb_shift;
+   void *cheb_y, *cheb_w;    /* device scratch: the two iterates that are not the caller's (2 x cheb_cols columns) and the
+                                operator product of the generic path (cheb_cols columns), cheb_ld elements apart */
+   int cheb_cols, cheb_wcols;
+   int64_t cheb_ld;
 };
 
 static size_t op_elem(hipk_dtype dt) { return dt == HIPK_F64 ? 8 : dt == HIPK_F32 ? 4 : dt == HIPK_C64 ? 16 : 8; }
@@ -80,6 +87,8 @@ extern "C" int primme_amd_operator_destroy(primme_amd_operator *op) {
    if (op->buf_lo) (void)hipFree(op->buf_lo);
    if (op->buf_hi) (void)hipFree(op->buf_hi);
    if (op->xfull) (void)hipFree(op->xfull);
+   if (op->cheb_y) (void)hipFree(op->cheb_y);
+   if (op->cheb_w) (void)hipFree(op->cheb_w);
    free(op);
    return 0;
 }
@@ -196,6 +205,167 @@ extern "C" void primme_amd_jacobi_precond(void *x, PRIMME_INT *ldx, void *y, PRI
             op->jacobi_fixed ? fixed : primme->ShiftsForPreconditioner + c0,
             1e-14 * (primme->aNorm >= 0.0 ? primme->aNorm : 1.0), (const char *)x + (size_t)c0 * lx * es, lx,
             (char *)y + (size_t)c0 * ly * es, ly, n);
+   }
+}
+
+/* ---- Chebyshev polynomial preconditioner K^-1 = p(A) (kernels in hipk_cheb.hip) -----------------------
+ * y = p(A) x is the d-th iterate of Chebyshev iteration for (A - sigma I) y = x from y_0 = 0 with the interval [lo, hi]:
+ *    tb = (hi + lo)/2 - sigma, dl = (hi - lo)/2, s1 = tb/dl, rho_1 = 1/s1, y_1 = x/tb,
+ *    rho_{k+1} = 1/(2 s1 - rho_k),  y_{k+1} = y_k + rho_{k+1} rho_k (y_k - y_{k-1}) + (2 rho_{k+1}/dl)(x - (A - sigma I) y_k),
+ * d - 1 operator applications.  Written as the linear combination the kernels take, with a = rho_{k+1} rho_k, b = 2 rho_{k+1}/dl:
+ *    y_{k+1} = (1 + a + b sigma) y_k - a y_{k-1} + b x - b A y_k.
+ * y_1 is never stored: step 1 gathers from x itself (coefficients divided by tb), step 2 reads x for y_{k-1} the same way.
+ * The iterates alternate between the two scratch panels, y_{k+1} over y_{k-1}; the last one goes to the caller's y. */
+/* Widest block for which the fused step is the default, per operator form: where the kernel trace shows it not slower than
+ * the operator product + cheb_update_kernel (profiles/cheb_step_kernels.md).  PRIMME_AMD_CHEB_FUSED=1 fuses at every width,
+ * PRIMME_AMD_CHEB_UNFUSED=1 at none. */
+#define CHEB_FUSE_PAT_MAXCOLS 8
+#define CHEB_FUSE_CSR_MAXCOLS 0
+static long g_cheb_applies, g_cheb_products, g_cheb_fused;
+extern "C" void primme_amd_chebyshev_stats(long *applies, long *operator_products, long *fused_steps) {
+   if (applies) *applies = g_cheb_applies;
+   if (operator_products) *operator_products = g_cheb_products;
+   if (fused_steps) *fused_steps = g_cheb_fused;
+   g_cheb_applies = g_cheb_products = g_cheb_fused = 0;
+}
+
+extern "C" int primme_amd_operator_gershgorin(primme_amd_operator *op, double *lo, double *hi) {
+   if (!op || !lo || !hi) return -1;
+   double b[2];
+   int rc = hipk_csr_gershgorin(op->A, NULL, b);
+   if (rc) return rc;
+   if (op->comm && primme_amd_comm_size(op->comm) > 1) {
+      /* every rank's pair, as bit patterns; an empty slab's (+inf, -inf) is neutral for min / max */
+      const int P = primme_amd_comm_size(op->comm);
+      int64_t mine[2], *all = (int64_t *)malloc((size_t)2 * P * sizeof(int64_t));
+      if (!all) return -2;
+      memcpy(mine, b, sizeof(mine));
+      rc = primme_amd_comm_allgather_i64(op->comm, mine, 2, all);
+      for (int q = 0; q < P && !rc; q++) {
+         double bq[2];
+         memcpy(bq, all + 2 * q, sizeof(bq));
+         if (bq[0] < b[0]) b[0] = bq[0];
+         if (bq[1] > b[1]) b[1] = bq[1];
+      }
+      free(all);
+      if (rc) return rc;
+   }
+   *lo = b[0]; *hi = b[1];
+   return 0;
+}
+
+extern "C" int primme_amd_operator_set_chebyshev(primme_amd_operator *op, int steps, double lo, double hi, int fixed, double shift) {
+   if (!op || steps < 1 || lo != lo) return -1;          /* lo = NaN: there is no sensible default for the lower end */
+   if (hi != hi) {                                       /* hi = NaN: the Gershgorin upper bound (collective over the ranks) */
+      double glo, ghi;
+      if (primme_amd_operator_gershgorin(op, &glo, &ghi)) return -1;
+      hi = ghi;
+   }
+   if (!(lo < hi)) return -1;
+   if (fixed && (shift != shift || (shift > lo && shift < hi))) return -1;
+   op->cheb_steps = steps; op->cheb_lo = lo; op->cheb_hi = hi; op->cheb_fixed = fixed != 0; op->cheb_shift = shift;
+   /* A/B knob, read when the preconditioner is configured (once per solve through the Python driver) */
+   const char *e = getenv("PRIMME_AMD_CHEB_UNFUSED");
+   op->cheb_unfused = e && atoi(e) != 0;
+   e = getenv("PRIMME_AMD_CHEB_FUSED");                  /* opt in to the fused step at every width (see CHEB_FUSE_*_MAXCOLS) */
+   op->cheb_fused_all = e && atoi(e) != 0;
+   return 0;
+}
+
+/* coefficients of step k (1 .. d-1) for one column; rho = rho_k on entry, rho_{k+1} on return */
+static void cheb_step_coef(double tb, double dl, double sigma, int k, double *rho, hipk_cheb_coef *cf, int c) {
+   const double s1 = tb / dl, rn = 1.0 / (2.0 * s1 - *rho), a = rn * *rho, b = 2.0 * rn / dl;
+   const double cy = 1.0 + a + b * sigma;
+   cf->cy[c] = k == 1 ? cy / tb : cy;          /* step 1: y_k is x / tb */
+   cf->cp[c] = k == 1 ? 0.0 : (k == 2 ? -a / tb : -a);      /* step 2: y_{k-1} is x / tb */
+   cf->cx[c] = b;
+   cf->cw[c] = k == 1 ? -b / tb : -b;
+   *rho = rn;
+}
+
+extern "C" void primme_amd_chebyshev_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
+      int *blockSize, struct primme_params *primme, int *ierr) {
+   primme_amd_operator *op = (primme_amd_operator *)primme->preconditioner;
+   void *stream = primme->queue ? (void *)*(hipStream_t *)primme->queue : NULL;
+   if (!op || op->cheb_steps < 1) { *ierr = 1; return; }
+   if (!op->cheb_fixed && primme->target != primme_smallest && primme->target != primme_largest) {
+      if (primme->printLevel > 0 && primme->outputFile)
+         fprintf(primme->outputFile, "primme_amd: the Chebyshev preconditioner follows the solver's shifts for the smallest / largest targets only (use a fixed shift)\n");
+      *ierr = 1;
+      return;
+   }
+   *ierr = 0;
+   if (*blockSize <= 0) return;
+   if (!stream) stream = hipk_ctx_stream(hipk_csr_ctx(op->A));
+   const hipk_dtype dt = hipk_csr_dtype(op->A);
+   const size_t es = op_elem(dt);
+   const int64_t m = hipk_csr_nrows(op->A);
+   const int64_t lx = *ldx * op->ldscale, ly = *ldy * op->ldscale;
+   const int d = op->cheb_steps;
+   const double lo = op->cheb_lo, hi = op->cheb_hi, dl = 0.5 * (hi - lo);
+   /* scratch for the widest chunk seen; columns on 16-byte boundaries */
+   const int want = *blockSize < HIPK_CHEB_MAXCOLS ? *blockSize : HIPK_CHEB_MAXCOLS;
+   const int64_t ld = (m + 3) / 4 * 4 + 4;
+   if (d > 1 && (want > op->cheb_cols || ld != op->cheb_ld)) {
+      if (op->cheb_y) (void)hipFree(op->cheb_y);
+      if (op->cheb_w) (void)hipFree(op->cheb_w);
+      op->cheb_y = op->cheb_w = NULL; op->cheb_cols = op->cheb_wcols = 0;
+      if (hipMalloc(&op->cheb_y, (size_t)ld * es * 2 * want) != hipSuccess) { *ierr = 1; return; }
+      op->cheb_cols = want; op->cheb_ld = ld;
+   }
+   /* the fused step serves real single-rank CSR operators whose vectors are what the solver hands over */
+   int fused_ok = !op->cheb_unfused && op->mode == 0 && op->ldscale == 1 && !(op->comm && primme_amd_comm_size(op->comm) > 1);
+   const int fuse_maxcols = hipk_csr_format(op->A) == 2 ? CHEB_FUSE_PAT_MAXCOLS : CHEB_FUSE_CSR_MAXCOLS;
+   char *P[2] = {(char *)op->cheb_y, (char *)op->cheb_y + (size_t)ld * es * op->cheb_cols};
+   for (int c0 = 0; c0 < *blockSize && !*ierr; c0 += HIPK_CHEB_MAXCOLS) {
+      const int nc = *blockSize - c0 < HIPK_CHEB_MAXCOLS ? *blockSize - c0 : HIPK_CHEB_MAXCOLS;
+      const char *xc = (const char *)x + (size_t)c0 * lx * es;
+      char *yc = (char *)y + (size_t)c0 * ly * es;
+      double sig[HIPK_CHEB_MAXCOLS], tb[HIPK_CHEB_MAXCOLS], rho[HIPK_CHEB_MAXCOLS];
+      hipk_cheb_coef cf;
+      memset(&cf, 0, sizeof(cf));
+      for (int c = 0; c < nc; c++) {
+         double sg = op->cheb_shift;
+         if (!op->cheb_fixed) {
+            /* the solver's shift, kept outside the open interval: at the clamp s1 = +-1 and the recurrence stays finite */
+            const int small = primme->target == primme_smallest;
+            sg = primme->ShiftsForPreconditioner ? primme->ShiftsForPreconditioner[c0 + c] : (small ? lo : hi);
+            if (small ? !(sg <= lo) : !(sg >= hi)) sg = small ? lo : hi;
+         }
+         sig[c] = sg; tb[c] = 0.5 * (hi + lo) - sg; rho[c] = dl / tb[c];
+         cf.cx[c] = 1.0 / tb[c];
+      }
+      g_cheb_applies += nc;
+      if (d == 1) {
+         *ierr = hipk_cheb_update(stream, dt, m, nc, &cf, xc, lx, NULL, 0, NULL, 0, NULL, 0, yc, ly) ? 1 : 0;
+         continue;
+      }
+      for (int k = 1; k < d && !*ierr; k++) {
+         for (int c = 0; c < nc; c++) cheb_step_coef(tb[c], dl, sig[c], k, &rho[c], &cf, c);
+         /* y_k: x (k = 1) or a scratch panel; y_{k-1}: none, x (k = 2) or the other panel; y_{k+1} over y_{k-1}, the last into y */
+         const char *yk = k == 1 ? xc : P[k % 2], *yp = k == 1 ? NULL : (k == 2 ? xc : P[(k + 1) % 2]);
+         const int64_t ldk = k == 1 ? lx : ld, ldp = k == 2 ? lx : ld;
+         char *out = k == d - 1 ? yc : P[(k + 1) % 2];
+         const int64_t ldo = k == d - 1 ? ly : ld;
+         int rc = 1;
+         if (fused_ok && (op->cheb_fused_all || nc <= fuse_maxcols)) {
+            rc = hipk_csr_cheb_step(op->A, stream, nc, &cf, xc, lx, yk, ldk, yp, ldp, out, ldo);
+            if (rc == 1) fused_ok = 0;            /* no fused form for this operator: the generic path from here on */
+            else if (rc == 0) g_cheb_fused += nc;
+         }
+         if (rc == 1) {
+            if (op->cheb_wcols < op->cheb_cols) {       /* the product's panel: only the generic path needs it */
+               if (op->cheb_w) (void)hipFree(op->cheb_w);
+               op->cheb_w = NULL; op->cheb_wcols = 0;
+               if (hipMalloc(&op->cheb_w, (size_t)ld * es * op->cheb_cols) != hipSuccess) { *ierr = 1; return; }
+               op->cheb_wcols = op->cheb_cols;
+            }
+            rc = primme_amd_operator_apply(op, stream, yk, ldk, op->cheb_w, ld, nc);
+            if (!rc) rc = hipk_cheb_update(stream, dt, m, nc, &cf, xc, lx, op->cheb_w, ld, yk, ldk, yp, ldp, out, ldo);
+         }
+         g_cheb_products += nc;
+         if (rc) *ierr = 1;
+      }
    }
 }
 

@@ -58,6 +58,9 @@ extern "C" int hipk_pat_grid(const hipk_pat *B, int num_cu);
 extern "C" double hipk_pat_bytes(const hipk_pat *B, int fused);
 extern "C" int hipk_pat_npatterns(const hipk_pat *B);
 extern "C" int hipk_pat_enabled(void);
+extern "C" int hipk_pat_cheb_step(const hipk_pat *B, void *hip_stream, int gx, const double cf[4], const void *xr, const void *yk, const void *yp, void *out);
+int hipk_cheb_gershgorin_rows(hipk_ctx *ctx, hipStream_t st, hipk_dtype dt, int64_t nrows, int64_t row0, const int32_t *rowptr,
+      const int32_t *colind, const void *val, double out[2]);
 extern "C" int hipk_pb_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t n, const int32_t *rp, const int32_t *ci, const void *val, hipk_pb **out);
 extern "C" int hipk_pb_matvec(const hipk_pb *B, void *hip_stream, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols);
 extern "C" void hipk_pb_destroy(hipk_pb *B);
@@ -324,13 +327,31 @@ csr_rows_block_kernel(const int32_t *__restrict__ tiles, int ntiles, const int32
 #define XS_MAX 3072
 #define XS_SMALL 1728      /* 192 window rows of 8 columns on the odd stride of 9: 39 KB of LDS per workgroup, still 4 per CU (1536 until round 6) */
 struct SpmmShift { double s[64]; int on; int nosplit; int evenstride; };
-template <typename T, int NC, int XS, bool C16>
+/* CHEB: the row sums are not stored but combined with the row's own entries of three panels — one step of the Chebyshev
+ * recurrence (hipk_cheb.hip): y(i,c) = cy[c] x(i,c) + cp[c] yp(i,c) + cx[c] xr(i,c) + cw[c] (A x)(i,c), x being the iterate
+ * the product gathers from (yp == NULL: no such term).  y may be yp (row-local), never x. */
+template <typename T> struct SpmmCheb { hipk_cheb_coef cf; const T *xr; int64_t ldr; const T *yp; int64_t ldp; };
+struct SpmmNoEp {};
+template <typename T, bool CHEB> struct SpmmEp { typedef SpmmNoEp type; };
+template <typename T> struct SpmmEp<T, true> { typedef SpmmCheb<T> type; };
+template <typename T, bool CHEB>
+__device__ __forceinline__ double spmm_epilogue(const typename SpmmEp<T, CHEB>::type &ep, double sum, const T *__restrict__ x, int64_t ldx, int64_t row, int c) {
+   if constexpr (CHEB) {
+      double o = ep.cf.cx[c] * (double)ep.xr[row + (size_t)c * ep.ldr];
+      o = fma(ep.cf.cy[c], (double)x[row + (size_t)c * ldx], o);
+      if (ep.yp) o = fma(ep.cf.cp[c], (double)ep.yp[row + (size_t)c * ep.ldp], o);
+      return fma(ep.cf.cw[c], sum, o);
+   } else {
+      return sum;
+   }
+}
+template <typename T, int NC, int XS, bool C16, bool CHEB = false>
 __global__ void __launch_bounds__(HIPK_BLOCK)
 csr_window_block_kernel(const int4 *__restrict__ tileinfo, const int2 *__restrict__ twin, int ntiles,
       const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colind, const uint16_t *__restrict__ col16, int64_t c16off,
       const T *__restrict__ val,
       const T *__restrict__ x, int64_t ldx, T *__restrict__ y, int64_t ldy, int ncols, int64_t row0,
-      SpmmShift sh) {
+      SpmmShift sh, typename SpmmEp<T, CHEB>::type ep) {
    __shared__ T sval[TILE_NNZ];
    __shared__ int32_t scol[TILE_NNZ];
    __shared__ int rp[TILE_ROWS + 1];
@@ -444,6 +465,7 @@ csr_window_block_kernel(const int4 *__restrict__ tileinfo, const int2 *__restric
             if (c0 + c < ncols) {
                double out = acc[c];
                if (sh.on) out = fma(-sh.s[c0 + c], (double)x[(int64_t)(r0 + r) + (size_t)(c0 + c) * ldx], out);
+               out = spmm_epilogue<T, CHEB>(ep, out, x, ldx, (int64_t)(r0 + r), c0 + c);
                y[r0 + r + (size_t)(c0 + c) * ldy] = (T)out;
             }
       }
@@ -461,6 +483,7 @@ csr_window_block_kernel(const int4 *__restrict__ tileinfo, const int2 *__restric
             if (threadIdx.x == 0) {
                double out = (red[0] + red[1]) + (red[2] + red[3]);
                if (sh.on) out = fma(-sh.s[c], (double)xc[row0 + r], out);
+               out = spmm_epilogue<T, CHEB>(ep, out, x, ldx, (int64_t)r, c);
                y[r + (size_t)c * ldy] = (T)out;
             }
             __syncthreads();
@@ -785,7 +808,7 @@ static bool csr_stream_nt(const hipk_csr *A) {
 
 template <typename T>
 static int csr_matvec_t(hipk_csr *A, hipStream_t stream, const T *x, int64_t ldx, T *y, int64_t ldy, int ncols,
-      const double *shift_host = NULL) {
+      const double *shift_host = NULL, const SpmmCheb<T> *cheb = NULL) {
    hipk_ctx *ctx = A->ctx;
    if ((A->halo_lo > 0 && !A->xlo) || (A->halo_hi > 0 && !A->xhi)) {
       fprintf(stderr, "primme_amd: matvec needs halo data (rows outside the local slab) but none was set\n");
@@ -801,21 +824,22 @@ static int csr_matvec_t(hipk_csr *A, hipStream_t stream, const T *x, int64_t ldx
     * read the 2-byte one when the matrix has it, the plain row-block kernel the 4-byte one) */
    double streamed = alg;
    if (A->kind == 0) {
-      const bool one_pat = A->pat && hipk_pat_enabled() && ncols == 1 && !shift_host;
-      const bool one_pb = A->pb && !shift_host && ncols <= pb_maxcols;
-      const bool win = A->halo_lo == 0 && A->halo_hi == 0 && ncols <= 64 && ((A->windowed && ncols >= 2) || shift_host);
+      const bool one_pat = A->pat && hipk_pat_enabled() && ncols == 1 && !shift_host && !cheb;
+      const bool one_pb = A->pb && !shift_host && !cheb && ncols <= pb_maxcols;
+      const bool win = A->halo_lo == 0 && A->halo_hi == 0 && ncols <= 64 && ((A->windowed && ncols >= 2) || shift_host || cheb);
       if (one_pat) streamed = hipk_pat_bytes(A->pat, 0);
       else if (one_pb) streamed = hipk_pb_bytes(A->pb) * ncols;
       else streamed = (double)A->nnz * (es + ((win || ncols == 1) && csr16(A) ? 2 : 4)) + (A->nrows + 1) * 4.0 + 2.0 * A->nrows * es * ncols;
    }
-   const int pslot = hipk_prof_begin_s(HIPK_PROF_SPMV, stream, alg, streamed);
-   if (A->pat && hipk_pat_enabled() && ncols == 1 && !shift_host) {
+   if (cheb) streamed += (cheb->yp ? 2.0 : 1.0) * A->nrows * es * ncols;      /* the epilogue's two other panels */
+   const int pslot = hipk_prof_begin_s(HIPK_PROF_SPMV, stream, cheb ? streamed : alg, streamed);
+   if (A->pat && hipk_pat_enabled() && ncols == 1 && !shift_host && !cheb) {
       const int rc = hipk_pat_matvec(A->pat, stream, hipk_pat_grid(A->pat, ctx->num_cu), x, y, A->halo_lo, A->halo_hi, A->xlo, A->xhi, NULL, 0, NULL,
             NULL, NULL);
       hipk_prof_end(pslot, stream);
       return rc;
    }
-   if (A->pb && !shift_host && ncols <= pb_maxcols) {
+   if (A->pb && !shift_host && !cheb && ncols <= pb_maxcols) {
       const int rc = hipk_pb_matvec(A->pb, stream, x, ldx, y, ldy, ncols);
       hipk_prof_end(pslot, stream);
       return rc;
@@ -834,7 +858,7 @@ static int csr_matvec_t(hipk_csr *A, hipStream_t stream, const T *x, int64_t ldx
       if (force < 0) { const char *env = getenv("HIPK_SPMM_NC"); force = env ? atoi(env) : 0; }
       if (nowin < 0) nowin = getenv("HIPK_NO_WINDOW") != NULL;
       const bool use_win = A->kind == 0 && A->halo_lo == 0 && A->halo_hi == 0 && ncols <= 64 &&
-                           ((A->windowed && ncols >= 2 && !nowin) || shift_host);
+                           ((A->windowed && ncols >= 2 && !nowin) || shift_host || cheb);
       if (use_win) {
          SpmmShift sh;
          sh.on = shift_host != NULL;
@@ -850,13 +874,16 @@ static int csr_matvec_t(hipk_csr *A, hipStream_t stream, const T *x, int64_t ldx
          static int bigxs = -1;                     /* HIPK_SPMM_BIG_WINDOW=1: always the large buffer (A/B knob) */
          if (bigxs < 0) bigxs = getenv("HIPK_SPMM_BIG_WINDOW") != NULL;
          const bool small = !bigxs && (int64_t)A->cw_max * (evenstride ? ncols : (ncols | 1)) <= XS_SMALL;
-#define LAUNCH_WIN(NCV, XSV, C16V) hipLaunchKernelGGL((csr_window_block_kernel<T, NCV, XSV, C16V>), dim3(gx), dim3(HIPK_BLOCK), 0, stream, A->tileinfo, A->twin, \
-                  A->ntiles, A->rowptr, A->colind, csr16(A), A->row0 - A->c16back, (const T *)A->values, x, ldx, y, ldy, ncols, A->x0, sh)
+#define LAUNCH_WIN_ARGS A->tileinfo, A->twin, A->ntiles, A->rowptr, A->colind, csr16(A), A->row0 - A->c16back, (const T *)A->values, x, ldx, y, ldy, ncols, A->x0, sh
+#define LAUNCH_WIN(NCV, XSV, C16V) do { \
+            if (cheb) hipLaunchKernelGGL((csr_window_block_kernel<T, NCV, XSV, C16V, true>), dim3(gx), dim3(HIPK_BLOCK), 0, stream, LAUNCH_WIN_ARGS, *cheb); \
+            else hipLaunchKernelGGL((csr_window_block_kernel<T, NCV, XSV, C16V, false>), dim3(gx), dim3(HIPK_BLOCK), 0, stream, LAUNCH_WIN_ARGS, SpmmNoEp()); } while (0)
 #define LAUNCH_WIN2(NCV, XSV) do { if (csr16(A)) LAUNCH_WIN(NCV, XSV, true); else LAUNCH_WIN(NCV, XSV, false); } while (0)
          if (ncols <= 2) { if (small) LAUNCH_WIN2(2, XS_SMALL); else LAUNCH_WIN2(2, XS_MAX); }
          else { if (small) LAUNCH_WIN2(4, XS_SMALL); else LAUNCH_WIN2(4, XS_MAX); }
 #undef LAUNCH_WIN2
 #undef LAUNCH_WIN
+#undef LAUNCH_WIN_ARGS
       } else if (ncols == 1 && force == 0) {
 #define LAUNCH_STREAM(C16V, NTV) hipLaunchKernelGGL((csr_stream_kernel<T, false, C16V, NTV>), dim3(gx), dim3(HIPK_BLOCK), 0, stream, \
                A->tileinfo, A->ntiles, A->rowptr, A->colind, csr16(A), A->row0 - A->c16back, (const T *)A->values, x, ldx, y, ldy, \
@@ -916,6 +943,53 @@ extern "C" int hipk_csr_matvec_shifted(hipk_csr *A, void *hip_stream, const void
    if (HIPK_IS_Z(A->dt)) return csr_matvec_z(A, st, x, ldx, y, ldy, ncols, shift_host);
    if (A->dt == HIPK_F64) return csr_matvec_t<double>(A, st, (const double *)x, ldx, (double *)y, ldy, ncols, shift_host);
    return csr_matvec_t<float>(A, st, (const float *)x, ldx, (float *)y, ldy, ncols, shift_host);
+}
+
+/* One step of the Chebyshev recurrence with the product inside (include/primme_amd_kernels.h, hipk_cheb.hip):
+ * Out = cy Yk + cp Yprev + cx X + cw A Yk.  The row-pattern form runs a column per launch (its kernel owns one column), the
+ * row-tile form all columns in one launch of the windowed block kernel.  Same conditions as hipk_csr_matvec_shifted, real
+ * matrices only; 1 = not covered. */
+extern "C" int hipk_csr_cheb_step(hipk_csr *A, void *hip_stream, int nx, const hipk_cheb_coef *coef, const void *X, int64_t ldx,
+      const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp, void *Out, int64_t ldo) {
+   if (!A || A->kind != 0 || A->halo_lo != 0 || A->halo_hi != 0 || A->x0 != A->row0 || A->xlen != A->nrows || HIPK_IS_Z(A->dt)) return 1;
+   if (nx <= 0 || A->nrows == 0) return 0;
+   if (nx > HIPK_CHEB_MAXCOLS || !coef || !X || !Yk || !Out || Out == Yk) return -1;
+   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : A->ctx->stream;
+   const size_t es = A->dt == HIPK_F64 ? 8 : 4;
+   if (A->pat && hipk_pat_enabled()) {
+      const int gx = hipk_pat_grid(A->pat, A->ctx->num_cu);
+      for (int c = 0; c < nx; c++) {
+         const double cf[4] = {coef->cy[c], coef->cp[c], coef->cx[c], coef->cw[c]};
+         const int pslot = hipk_prof_begin_s(HIPK_PROF_SPMV, st, hipk_pat_bytes(A->pat, 0) + (Yprev ? 2.0 : 1.0) * A->nrows * es,
+               hipk_pat_bytes(A->pat, 0) + (Yprev ? 2.0 : 1.0) * A->nrows * es);
+         const int rc = hipk_pat_cheb_step(A->pat, st, gx, cf, (const char *)X + (size_t)c * ldx * es, (const char *)Yk + (size_t)c * ldk * es,
+               Yprev ? (const char *)Yprev + (size_t)c * ldp * es : NULL, (char *)Out + (size_t)c * ldo * es);
+         hipk_prof_end(pslot, st);
+         if (rc) return rc;
+      }
+      return 0;
+   }
+   if (A->dt == HIPK_F64) {
+      const SpmmCheb<double> ep = {*coef, (const double *)X, ldx, (const double *)Yprev, ldp};
+      return csr_matvec_t<double>(A, st, (const double *)Yk, ldk, (double *)Out, ldo, nx, NULL, &ep);
+   }
+   const SpmmCheb<float> ep = {*coef, (const float *)X, ldx, (const float *)Yprev, ldp};
+   return csr_matvec_t<float>(A, st, (const float *)Yk, ldk, (float *)Out, ldo, nx, NULL, &ep);
+}
+
+/* Gershgorin bounds of the local rows (include/primme_amd_kernels.h).  The Laplacian stencil form has diagonal 2 d and 2 d
+ * off-diagonal entries -1 in its interior rows: [0, 4 d] whatever the slab (a slab without an interior row is one grid line
+ * at most: the bound still encloses its discs). */
+extern "C" int hipk_csr_gershgorin(hipk_csr *A, void *hip_stream, double out[2]) {
+   if (!A || !out) return -1;
+   if (A->kind == 1) {
+      const int d = (A->sz > 1) ? 3 : (A->sy > 1 ? 2 : 1);
+      if (A->nrows == 0) { out[0] = INFINITY; out[1] = -INFINITY; }
+      else { out[0] = 0.0; out[1] = 4.0 * d; }
+      return 0;
+   }
+   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : A->ctx->stream;
+   return hipk_cheb_gershgorin_rows(A->ctx, st, A->dt, A->nrows, A->row0, A->rowptr, A->colind, A->values, out);
 }
 
 /* y = A (a x), xout = a x, dot_dev[0] = xout' y with a = 1/sqrt(norm2_dev[0]) — see csr_stream_kernel<T, true>.

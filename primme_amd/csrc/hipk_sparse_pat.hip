@@ -71,10 +71,17 @@ template <typename T> __device__ __forceinline__ void pat_store(T *p, T v) {
 /* one trip of a lane: RPL rows, 256 apart.  Every gather of the trip is issued before the first product; GUARD: the chunk may
  * reach past the end of the slab — a row past the end works on the last row (not stored); an entry past a row's length gathers
  * the row's own x (table: offset 0, value 0) and is not added */
-template <typename T, int ML, int RPL, bool FUSED, bool HALO, bool GUARD>
+/* CHEB (hipk_cheb.hip: one step of the Chebyshev recurrence with the product inside): the row sum s is not stored as it is but as
+ * cy x(r) + cp yp(r) + cx xr(r) + cw s, x being the iterate the product gathers from; y may be yp (row-local), never x */
+template <typename T> struct pat_cheb { double cy, cp, cx, cw; const T *xr, *yp; };
+struct pat_nocheb {};
+template <typename T, bool CHEB> struct pat_ep { typedef pat_nocheb type; };
+template <typename T> struct pat_ep<T, true> { typedef pat_cheb<T> type; };
+
+template <typename T, int ML, int RPL, bool FUSED, bool HALO, bool GUARD, bool CHEB = false>
 __device__ __forceinline__ void pat_trip(const int (&p)[RPL], const int64_t (&r)[RPL], const double *s_val, const int32_t *s_off,
       const int32_t *s_len, int64_t nrows, const T *__restrict__ x, T *__restrict__ y, int64_t halo_lo, const T *__restrict__ xlo,
-      const T *__restrict__ xhi, double a, T *__restrict__ xout, double &dotp) {
+      const T *__restrict__ xhi, double a, T *__restrict__ xout, double &dotp, const typename pat_ep<T, CHEB>::type &ch) {
    const int64_t last = nrows - 1;
    double xg[RPL][ML], xo[RPL];
 #pragma unroll
@@ -92,7 +99,7 @@ __device__ __forceinline__ void pat_trip(const int (&p)[RPL], const int64_t (&r)
             xg[u][e] = (double)x[l];
          }
       }
-      if (FUSED) xo[u] = (double)x[rc];
+      if (FUSED || CHEB) xo[u] = (double)x[rc];
    }
 #pragma unroll
    for (int u = 0; u < RPL; u++) {
@@ -105,7 +112,13 @@ __device__ __forceinline__ void pat_trip(const int (&p)[RPL], const int64_t (&r)
          s = e < len ? t : s;
       }
       if (!GUARD || r[u] < nrows) {
-         const T yt = (T)s;
+         T yt = (T)s;
+         if constexpr (CHEB) {
+            double o = ch.cx * (double)ch.xr[r[u]];
+            o = fma(ch.cy, xo[u], o);
+            if (ch.yp) o = fma(ch.cp, (double)ch.yp[r[u]], o);
+            yt = (T)fma(ch.cw, s, o);
+         }
          pat_store(y + r[u], yt);
          if (FUSED) {
             const double xown = (double)(T)(a * xo[u]);
@@ -155,22 +168,29 @@ template <typename T> __device__ __forceinline__ void pat_bstore2(__amdgpu_buffe
  *   rx: x from element (first row of the chunk + minoff) to its end (offsets are biased by -minoff, so every byte offset is
  *   unsigned, and the range check is exact);  ry / ro: y, xout from the chunk's first row;  rowb[u]: byte offset of the lane's
  *   u-th pair within the chunk */
-template <typename T, int ML, int RPL, bool FUSED>
+/* CHEB: ro is the descriptor of the right-hand side xr, rq the one of yp (both from the chunk's first row, as ry) */
+template <typename T, int ML, int RPL, bool FUSED, bool CHEB = false>
 __device__ __forceinline__ void pat_trip_inner(const int (&p)[2 * RPL], const double *s_val, const int32_t *s_off, const int32_t *s_len,
       __amdgpu_buffer_rsrc_t rx, __amdgpu_buffer_rsrc_t ry, __amdgpu_buffer_rsrc_t ro, int32_t minoff, bool near,
-      const uint32_t (&rowb)[RPL], double a, double &dotp) {
+      const uint32_t (&rowb)[RPL], double a, double &dotp, const typename pat_ep<T, CHEB>::type &ch, __amdgpu_buffer_rsrc_t rq) {
    constexpr int SH = sizeof(T) == 8 ? 3 : 2;
    const uint32_t ownb = (uint32_t)(-minoff) << SH;
    double xa[RPL][ML], xb[RPL][ML], oa[RPL], ob[RPL];
+   double ra[RPL], rb[RPL], qa[RPL], qb[RPL];        /* CHEB: the pair's entries of xr and yp */
 #pragma unroll
    for (int u = 0; u < RPL; u++) {
       const int pa = p[2 * u], pb = p[2 * u + 1];
+      if constexpr (CHEB) {
+         pat_bload2<T>(ro, rowb[u], 0, ra[u], rb[u]);
+         qa[u] = 0.0; qb[u] = 0.0;
+         if (ch.yp) pat_bload2<T>(rq, rowb[u], 0, qa[u], qb[u]);
+      }
       /* both rows with the first row's offsets: one access per entry for the pair (an entry past the end of x reads as 0: the
        * descriptor's range check) ... */
 #pragma unroll
       for (int e = 0; e < ML; e++)
          pat_bload2<T>(rx, rowb[u] + ((uint32_t)(s_off[pa * ML + e] - minoff) << SH), 0, xa[u][e], xb[u][e]);
-      if (FUSED) pat_bload2<T>(rx, rowb[u] + ownb, 0, oa[u], ob[u]);
+      if (FUSED || CHEB) pat_bload2<T>(rx, rowb[u] + ownb, 0, oa[u], ob[u]);
       /* ... and where the second row has a pattern of its own (the few lanes whose pair straddles a change) its entries again.
        * With the first row's offsets the second element of such a pair's access can lie one past the end of x (the first row
        * references the last column), and what a partially out-of-range access returns for its in-range half is not something
@@ -199,7 +219,11 @@ __device__ __forceinline__ void pat_trip_inner(const int (&p)[2 * RPL], const do
          sa = e < la ? ta : sa;
          sb = e < lb ? tb : sb;
       }
-      const T ya = (T)sa, yb = (T)sb;
+      T ya = (T)sa, yb = (T)sb;
+      if constexpr (CHEB) {
+         const double ea = fma(ch.cp, qa[u], fma(ch.cy, oa[u], ch.cx * ra[u])), eb = fma(ch.cp, qb[u], fma(ch.cy, ob[u], ch.cx * rb[u]));
+         ya = (T)fma(ch.cw, sa, ea); yb = (T)fma(ch.cw, sb, eb);
+      }
       pat_bstore2<T>(ry, rowb[u], 0, ya, yb);
       if (FUSED) {
          const double wa = (double)(T)(a * oa[u]), wb = (double)(T)(a * ob[u]);
@@ -234,12 +258,13 @@ __device__ __forceinline__ void pat_ids(const uint8_t *__restrict__ pid, int64_t
  * contiguous window and the +-nx / +-plane neighbours of a stencil row are found in ITS L2.
  * RPL rows per lane and trip (256 apart: every access of a wave stays unit-stride): all their gathers are issued before
  * the first product — the bytes a wave keeps in flight are what bounds a kernel whose rows need 9 bytes from HBM. */
-template <typename T, int ML, int RPL, int WPS, bool FUSED, bool HALO>
+template <typename T, int ML, int RPL, int WPS, bool FUSED, bool HALO, bool CHEB = false>
 __global__ void __launch_bounds__(HIPK_BLOCK, WPS)
 pat_kernel(const uint8_t *__restrict__ pid, const int32_t *__restrict__ toff, const double *__restrict__ tval,
       const int32_t *__restrict__ tlen, int npat, int64_t nrows, const T *__restrict__ x, T *__restrict__ y,
       int64_t halo_lo, const T *__restrict__ xlo, const T *__restrict__ xhi, const double *__restrict__ norm2, int np2,
-      T *__restrict__ xout, double *__restrict__ partials, hipk_fin_args fa, int32_t minoff, int32_t maxoff) {
+      T *__restrict__ xout, double *__restrict__ partials, hipk_fin_args fa, int32_t minoff, int32_t maxoff,
+      typename pat_ep<T, CHEB>::type ch) {
    extern __shared__ double pat_sh[];
    __shared__ int s_last;
    __shared__ double s_n2[4];
@@ -286,12 +311,19 @@ pat_kernel(const uint8_t *__restrict__ pid, const int32_t *__restrict__ toff, co
          const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(y + r0), 0, (int)(ybytes < 0x7fffffff ? ybytes : 0x7fffffff), 0x00020000);
          const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)((FUSED ? xout : y) + r0), 0, (int)(ybytes < 0x7fffffff ? ybytes : 0x7fffffff), 0x00020000);
          const bool near = r0 + CH + maxoff >= nrows;               /* some row of the chunk may reference the last column */
-         pat_trip_inner<T, ML, RPL, FUSED>(p, s_val, s_off, s_len, rx, ry, ro, minoff, near, rowb, a, dotp);
+         if constexpr (CHEB) {
+            const int rbytes = (int)(ybytes < 0x7fffffff ? ybytes : 0x7fffffff);
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void *)(ch.xr + r0), 0, rbytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)((ch.yp ? ch.yp : ch.xr) + r0), 0, rbytes, 0x00020000);
+            pat_trip_inner<T, ML, RPL, FUSED, true>(p, s_val, s_off, s_len, rx, ry, rr, minoff, near, rowb, a, dotp, ch, rq);
+         } else {
+            pat_trip_inner<T, ML, RPL, FUSED, false>(p, s_val, s_off, s_len, rx, ry, ro, minoff, near, rowb, a, dotp, ch, ro);
+         }
       } else {
          int64_t r[NR];
 #pragma unroll
          for (int v = 0; v < NR; v++) r[v] = r0 + 2 * (threadIdx.x + (int64_t)(v >> 1) * HIPK_BLOCK) + (v & 1);
-         pat_trip<T, ML, NR, FUSED, HALO, true>(p, r, s_val, s_off, s_len, nrows, x, y, halo_lo, xlo, xhi, a, xout, dotp);
+         pat_trip<T, ML, NR, FUSED, HALO, true, CHEB>(p, r, s_val, s_off, s_len, nrows, x, y, halo_lo, xlo, xhi, a, xout, dotp, ch);
       }
    }
    if (FUSED) {
@@ -411,7 +443,7 @@ static void pat_launch_ml(const hipk_pat *B, hipStream_t st, int gx, const T *x,
       const double *norm2, int np2, T *xout, double *partials, const hipk_fin_args &fa) {
    const size_t shm = (size_t)B->npat * B->ml * 12 + (size_t)B->npat * 4 + 8;
 #define PATL(MLV) hipLaunchKernelGGL((pat_kernel<T, MLV, PAT_RPL_FOR(MLV), HIPK_PAT_WPS, FUSED, HALO>), dim3(gx), dim3(HIPK_BLOCK), shm, st, B->pid, B->toff, B->tval, B->tlen, B->npat, \
-         B->nrows, x, y, halo_lo, xlo, xhi, norm2, np2, xout, partials, fa, B->minoff, B->maxoff)
+         B->nrows, x, y, halo_lo, xlo, xhi, norm2, np2, xout, partials, fa, B->minoff, B->maxoff, pat_nocheb())
    switch (B->ml) {
    case 3: PATL(3); break;
    case 5: PATL(5); break;
@@ -438,6 +470,33 @@ extern "C" int hipk_pat_matvec(const hipk_pat *B, void *hip_stream, int gx, cons
              else pat_launch_ml<TT, false, false>(B, st, gx, (const TT *)x, (TT *)y, halo_lo, (const TT *)xlo, (const TT *)xhi, norm2, np2, (TT *)xout, partials, fa); } } while (0)
    if (B->dt == HIPK_F64) PATD(double); else PATD(float);
 #undef PATD
+   HIPK_CHECK(hipGetLastError());
+   return 0;
+}
+
+/* out = cf[0] yk + cf[1] yp + cf[2] xr + cf[3] (A yk): one step of the Chebyshev recurrence (hipk_cheb.hip) as an epilogue of the
+ * one-column product above — same traversal, same pattern bytes; per row 4 vector streams instead of the 2 + 5 of the product
+ * followed by the update.  yp may be NULL; out may be yp, never yk.  A slab without halo (the caller checks). */
+template <typename T>
+static void pat_cheb_launch(const hipk_pat *B, hipStream_t st, int gx, const double cf[4], const T *xr, const T *yk, const T *yp, T *out) {
+   const size_t shm = (size_t)B->npat * B->ml * 12 + (size_t)B->npat * 4 + 8;
+   const pat_cheb<T> ch = {cf[0], cf[1], cf[2], cf[3], xr, yp};
+   hipk_fin_args fa;
+   memset(&fa, 0, sizeof(fa));
+#define PATC(MLV) hipLaunchKernelGGL((pat_kernel<T, MLV, PAT_RPL_FOR(MLV), HIPK_PAT_WPS, false, false, true>), dim3(gx), dim3(HIPK_BLOCK), shm, st, B->pid, B->toff, B->tval, \
+         B->tlen, B->npat, B->nrows, yk, out, (int64_t)0, (const T *)NULL, (const T *)NULL, (const double *)NULL, 0, (T *)NULL, (double *)NULL, fa, B->minoff, B->maxoff, ch)
+   switch (B->ml) {
+   case 3: PATC(3); break;
+   case 5: PATC(5); break;
+   case 7: PATC(7); break;
+   default: PATC(8); break;
+   }
+#undef PATC
+}
+extern "C" int hipk_pat_cheb_step(const hipk_pat *B, void *hip_stream, int gx, const double cf[4], const void *xr, const void *yk, const void *yp, void *out) {
+   hipStream_t st = (hipStream_t)hip_stream;
+   if (B->dt == HIPK_F64) pat_cheb_launch<double>(B, st, gx, cf, (const double *)xr, (const double *)yk, (const double *)yp, (double *)out);
+   else pat_cheb_launch<float>(B, st, gx, cf, (const float *)xr, (const float *)yk, (const float *)yp, (float *)out);
    HIPK_CHECK(hipGetLastError());
    return 0;
 }
