@@ -162,10 +162,14 @@ int hipk_cheb_gershgorin_rows(hipk_ctx *ctx, hipStream_t st, hipk_dtype dt, int6
    default: hipLaunchKernelGGL((cheb_gershgorin_kernel<float, true>), dim3(gx), dim3(HIPK_BLOCK), 0, st, nrows, row0, rowptr, colind, (const float *)val, part); break;
    }
    hipLaunchKernelGGL(cheb_minmax_kernel, dim3(1), dim3(HIPK_BLOCK), 0, st, part, gx, part + 2 * (size_t)gx);
+   /* `out` is the caller's memory (a stack variable, a ctypes buffer): the result comes back through the context's pinned
+    * staging buffer like every other read-back (hipk_download), never by an asynchronous copy into pageable pages */
    hipError_t e = hipGetLastError();
-   if (e == hipSuccess) e = hipMemcpyAsync(out, part + 2 * (size_t)gx, 2 * sizeof(double), hipMemcpyDeviceToHost, st);
    if (e == hipSuccess) e = hipStreamSynchronize(st);
+   double res[2] = {INFINITY, -INFINITY};
+   const int rc = e == hipSuccess ? hipk_download(ctx, res, part + 2 * (size_t)gx, sizeof(res)) : -1;
    (void)hipFree(part);
-   if (e != hipSuccess) { fprintf(stderr, "primme_amd: Gershgorin reduction failed: %s\n", hipGetErrorString(e)); return -1; }
+   if (e != hipSuccess || rc) { fprintf(stderr, "primme_amd: Gershgorin reduction failed: %s\n", e != hipSuccess ? hipGetErrorString(e) : "read-back"); return -1; }
+   out[0] = res[0]; out[1] = res[1];
    return 0;
 }

@@ -859,8 +859,21 @@ def _lattice_csr(n, rng):
     return np.cumsum(rp).astype(np.int32), np.array(cols, dtype=np.int32), np.array(vals)
 
 
+def _lattice8_csr(n):
+    """a non-symmetric 1-D lattice operator with the neighbours -4 .. 3, eight different values in a row (all exact in float) and
+    two alternating site types: the widest row-pattern table (8 entries), 2 patterns away from the ends"""
+    i = np.arange(n)[:, None]
+    d = np.arange(-4, 4)[None, :]
+    vals = np.array([0.25, -0.5, 0.75, -1.0, 2.0, -1.25, 0.375, -0.625]) + 0 * i
+    vals[:, 4] += 0.5 * (i[:, 0] % 2)
+    vals[:, 7] -= 0.25 * (i[:, 0] % 2)
+    keep = (i + d >= 0) & (i + d < n)
+    rp = np.zeros(n + 1, dtype=np.int64); np.cumsum(keep.sum(axis=1), out=rp[1:])
+    return rp.astype(np.int32), (i + d)[keep].astype(np.int32), vals[keep]
+
+
 @pytest.mark.parametrize("dt", [F.HIPK_F64, F.HIPK_F32])
-@pytest.mark.parametrize("case", ["lap1d", "lap1d_full_chunks", "lap2d", "lap2d_full_chunks", "lap2d_big", "lap3d", "lattice", "lap3d_slab", "random"])
+@pytest.mark.parametrize("case", ["lap1d", "lap1d_full_chunks", "lap2d", "lap2d_full_chunks", "lap2d_big", "lap3d", "lattice", "lattice8", "lap3d_slab", "random"])
 def test_csr_row_pattern_form(built, dt, case):
     """Matrices whose rows repeat are served by the row-pattern form (csrc/hipk_sparse_pat.hip: one byte per row + a pattern
     table, one lane per row) for one-column products.  Checked: hipk_csr_create picks it for stencils / lattice operators
@@ -877,6 +890,7 @@ def test_csr_row_pattern_form(built, dt, case):
     elif case == "lap2d_big": rp, ci, va, n = problems.laplacian_csr((1234, 1111))     # > 2 chunks per workgroup of every XCD
     elif case == "lap3d": rp, ci, va, n = problems.laplacian_csr((64, 65, 66))
     elif case == "lattice": n = 40003; rp, ci, va = _lattice_csr(n, rng)
+    elif case == "lattice8": n = 6001; rp, ci, va = _lattice8_csr(n)      # table width 8; 12 chunks on a grid of 8: two trips per workgroup
     elif case == "lap3d_slab":
         dims = (23, 19, 17); n = int(np.prod(dims)); row0 = 2000
         rp, ci, va, _ = problems.laplacian_csr(dims, row0=row0, nrows=3003)
