@@ -409,6 +409,18 @@ int hipk_cheb_update(void *hip_stream, hipk_dtype dt, int64_t m, int nx, const h
 int hipk_csr_cheb_step(hipk_csr *A, void *hip_stream, int nx, const hipk_cheb_coef *coef, const void *X, int64_t ldx,
       const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp, void *Out, int64_t ldo);
 int hipk_csr_gershgorin(hipk_csr *A, void *hip_stream, double out[2]);
+/* hipk_csr_cheb_step_gather: the step for a RECTANGULAR matrix (hipk_csr_create_rect), Out = cy Yk + cp Yprev + cx X + cw (A G) in
+ * one pass over A's row tiles.  G has ncols(A) rows and is the only gathered panel; X, Yk, Yprev, Out have nrows(A) rows and
+ * are row-local.  Yk and Yprev may each be NULL; Out may be Yprev or Yk, never G.  All nx <= HIPK_CHEB_MAXCOLS columns in one
+ * launch.  Same order as above (cx x, fma(cy, yk), fma(cp, yp), fma(cw, row sum)) on the double row sum hipk_csr_matvec forms
+ * for this matrix and width: in double the result is that of hipk_csr_matvec followed by hipk_cheb_update, bit for bit.
+ * -1: argument error; 1: the matrix has no row-tile form (panel-blocked, row patterns, stencil, halo, complex dtype) and the
+ * caller runs that pair.  For p(A'A): z = A y_k, then this on A' with G = z — A'z is neither written nor read back.
+ * hipk_csr_abs_rowsum_max: max_i sum_j |a_ij| over the local rows (HIPK_F64 / HIPK_F32; one pass, fixed-order second stage,
+ * complete on return; 0 for an empty matrix). */
+int hipk_csr_cheb_step_gather(hipk_csr *A, void *hip_stream, int nx, const hipk_cheb_coef *coef, const void *X, int64_t ldx,
+      const void *G, int64_t ldg, const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp, void *Out, int64_t ldo);
+int hipk_csr_abs_rowsum_max(hipk_csr *A, void *hip_stream, double *out);
 
 /* ---- Rayleigh-Ritz small solve on the device (reference solve_projection.c:188-331 calls xHEEVX,
  * blaslapack.c:1024-1143).  Symmetric n x n (n <= 64), upper triangle of A_host referenced;

@@ -157,6 +157,27 @@ int primme_amd_svds_operator_set_jacobi(primme_amd_svds_operator *op, const int3
       const int32_t *colind_host, const void *values_host, double shift);
 void primme_amd_svds_jacobi_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy, int *blockSize,
       int *mode, struct primme_svds_params *primme_svds, int *ierr);
+/* Ready-made applyPreconditioner: the Chebyshev polynomial preconditioner of primme_amd.h for singular value problems.
+ * The arguments of set_chebyshev are in SINGULAR VALUE units: [slo, shi] is the part of the singular spectrum to damp, sshift
+ * the target outside (slo, shi) (an end of the interval is allowed).  With lo = slo^2, hi = shi^2, sigma = sshift^2 let p be
+ * the polynomial of primme_amd_chebyshev_precond: the steps-th Chebyshev iterate for (M - sigma I) y = x from y = 0.  Then
+ *    mode primme_svds_op_AtA        (n-vectors)            y = p(A'A) x
+ *    mode primme_svds_op_AAt        (m-vectors)            y = p(AA') x
+ *    mode primme_svds_op_augmented  ([v; u], n then m)     y = (B + sshift I) diag(p(A'A), p(AA')) x,  B = [0 A'; A 0]
+ *    any other mode                                        *ierr = 1
+ * On an eigenvector of B with eigenvalue l the augmented result is (1 - q(l^2)) / (l - sshift), q the residual polynomial: an
+ * approximation of (B - sshift I)^-1 that is symmetric and commutes with B, for the smallest, largest and interior targets.
+ * set_chebyshev returns -1 for steps < 1, slo < 0 or NaN, slo >= shi, slo < sshift < shi, sshift < 0 or NaN; -44 for a
+ * row-partitioned operator; shi = NaN takes primme_amd_svds_operator_norm_bound = sqrt(|A|_1 |A|_inf) >= sigma_max.
+ * primme_svds->preconditioner = the operator handle, which owns the scratch panels; blocks wider than 8 go in chunks of 8.
+ * For the real-equivalent form of a complex matrix (set_complex) the recurrence runs unchanged on the 2n / 2m real rows.
+ * The products inside are not numMatvecs: primme_amd_chebyshev_stats counts them, one per vector and application of A or A'
+ * (2 (steps - 1) in the normal-equation modes, 4 (steps - 1) + 2 in the augmented one).  PRIMME_AMD_CHEB_UNFUSED /
+ * PRIMME_AMD_CHEB_FUSED as in primme_amd.h. */
+int primme_amd_svds_operator_set_chebyshev(primme_amd_svds_operator *op, int steps, double slo, double shi, double sshift);
+int primme_amd_svds_operator_norm_bound(primme_amd_svds_operator *op, double *bound);
+void primme_amd_svds_chebyshev_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy, int *blockSize,
+      int *mode, struct primme_svds_params *ps, int *ierr);
 
 #ifdef __cplusplus
 }

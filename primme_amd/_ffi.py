@@ -289,6 +289,19 @@ def declare_chebyshev(lib):
     lib.hipk_csr_cheb_step.restype = C.c_int
     lib.hipk_csr_gershgorin.argtypes = [_vp, _vp, _dp]
     lib.hipk_csr_gershgorin.restype = C.c_int
+    # the singular value version (include/primme_amd_svds.h) and its kernels
+    lib.primme_amd_svds_operator_set_chebyshev.argtypes = [_vp, _i, C.c_double, C.c_double, C.c_double]
+    lib.primme_amd_svds_operator_set_chebyshev.restype = C.c_int
+    lib.primme_amd_svds_operator_norm_bound.argtypes = [_vp, _dp]
+    lib.primme_amd_svds_operator_norm_bound.restype = C.c_int
+    lib.primme_amd_svds_chebyshev_precond.argtypes = [_vp, P(PRIMME_INT), _vp, P(PRIMME_INT), P(_i), P(_i), _vp, P(_i)]
+    lib.primme_amd_svds_chebyshev_precond.restype = None
+    lib.primme_amd_svds_operator_set_complex.argtypes = [_vp, _i]
+    lib.primme_amd_svds_operator_set_complex.restype = C.c_int
+    lib.hipk_csr_cheb_step_gather.argtypes = [_vp, _vp, _i, P(HipkChebCoef), _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]
+    lib.hipk_csr_cheb_step_gather.restype = C.c_int
+    lib.hipk_csr_abs_rowsum_max.argtypes = [_vp, _vp, _dp]
+    lib.hipk_csr_abs_rowsum_max.restype = C.c_int
 
 
 _cache = {}

@@ -394,6 +394,15 @@ struct primme_amd_svds_operator {
    hipk_dtype dt;
    void *jac_r, *jac_c;          /* Jacobi for the normal equations: row / column sums of squares - shift^2 */
    int cplx;                     /* real-equivalent form of a complex matrix: leading dimensions arrive in complex elements */
+   /* Chebyshev polynomial preconditioner (primme_amd_svds_chebyshev_precond): steps = 0 until configured; lo, hi, sigma are the
+    * squares of the singular value bounds.  Scratch, side 0 = n-vectors (rows of A'), side 1 = m-vectors (rows of A): two
+    * panels of cheb_cols columns each (the iterates, and the product with the first factor for the other side) and, for the
+    * unfused path only, the product with the second factor */
+   int cheb_steps, cheb_unfused, cheb_fused_all;
+   double cheb_lo, cheb_hi, cheb_sigma, cheb_sshift;
+   void *cheb_p[2], *cheb_w[2];
+   int cheb_cols, cheb_wcols[2];
+   int64_t cheb_ld[2];
 };
 
 extern "C" int primme_amd_svds_operator_create(primme_amd_svds_operator **out, hipk_ctx *ctx, int dt,
@@ -426,6 +435,10 @@ extern "C" int primme_amd_svds_operator_destroy(primme_amd_svds_operator *op) {
    if (op->full) (void)hipFree(op->full);
    if (op->jac_r) (void)hipFree(op->jac_r);
    if (op->jac_c) (void)hipFree(op->jac_c);
+   for (int i = 0; i < 2; i++) {
+      if (op->cheb_p[i]) (void)hipFree(op->cheb_p[i]);
+      if (op->cheb_w[i]) (void)hipFree(op->cheb_w[i]);
+   }
    hipk_csr_destroy(op->A); hipk_csr_destroy(op->At);
    free(op);
    return 0;
@@ -487,6 +500,161 @@ extern "C" void primme_amd_svds_jacobi_precond(void *x, PRIMME_INT *ldx, void *y
          rc = hipk_jacobi_apply(stream, dt, n, op->jac_c, zeros, min_den, xc, *ldx, yc, *ldy, nb);
          if (!rc) rc = hipk_jacobi_apply(stream, dt, m, op->jac_r, zeros, min_den, xc + (size_t)n * es, *ldx, yc + (size_t)n * es, *ldy, nb);
       } else rc = 1;
+   }
+   *ierr = rc ? 1 : 0;
+}
+
+/* ---- Chebyshev polynomial preconditioner for the singular value solver ---------------------------------
+ * With lo = slo^2, hi = shi^2, sigma = sshift^2 and p the polynomial of primme_amd_chebyshev_precond above (the steps-th
+ * Chebyshev iterate for (M - sigma I) y = x from y = 0):
+ *    primme_svds_op_AtA        y = p(A'A) x
+ *    primme_svds_op_AAt        y = p(AA') x
+ *    primme_svds_op_augmented  y = (B + sshift I) diag(p(A'A), p(AA')) x,  B = [0 A'; A 0], x = [v; u]
+ * (on an eigenvector of B with eigenvalue l the last one is (1 - q(l^2)) / (l - sshift): symmetric, commutes with B).
+ * One step of p(A'A): z = A y_k (plain product), then Out = cy y_k + cp y_{k-1} + cx x + cw A'z — in one pass over A' with
+ * hipk_csr_cheb_step_gather (G = z), or A'z into a product panel + hipk_cheb_update.  Widest block for which the one-pass
+ * step is the default: where the kernel trace shows it not slower.  It is slower at both widths measured (66.7 against 62.2 us
+ * at one column, 381 against 316 us at eight, A' of a 4 M x 3 M band matrix; profiles/svds_cheb_step_kernels.md), so the
+ * generic pair is the default; PRIMME_AMD_CHEB_FUSED=1 takes the one-pass step at every width, PRIMME_AMD_CHEB_UNFUSED=1 at none. */
+#define CHEB_FUSE_GATHER_MAXCOLS 0
+
+extern "C" int primme_amd_svds_operator_norm_bound(primme_amd_svds_operator *op, double *bound) {
+   if (!op || !bound) return -1;
+   if (op->comm) return -44;
+   double rinf = 0.0, r1 = 0.0;
+   int rc = hipk_csr_abs_rowsum_max(op->A, NULL, &rinf);
+   if (!rc) rc = hipk_csr_abs_rowsum_max(op->At, NULL, &r1);
+   if (rc) return rc;
+   *bound = sqrt(rinf * r1);            /* |A|_2^2 <= |A|_1 |A|_inf */
+   return 0;
+}
+
+extern "C" int primme_amd_svds_operator_set_chebyshev(primme_amd_svds_operator *op, int steps, double slo, double shi, double sshift) {
+   if (!op) return -1;
+   if (op->comm) return -44;
+   if (steps < 1 || slo != slo || slo < 0.0 || sshift != sshift || sshift < 0.0) return -1;    /* singular value units: nothing is negative */
+   if (shi != shi && primme_amd_svds_operator_norm_bound(op, &shi)) return -1;
+   if (!(slo < shi) || (sshift > slo && sshift < shi)) return -1;
+   op->cheb_steps = steps; op->cheb_lo = slo * slo; op->cheb_hi = shi * shi; op->cheb_sigma = sshift * sshift; op->cheb_sshift = sshift;
+   const char *e = getenv("PRIMME_AMD_CHEB_UNFUSED");
+   op->cheb_unfused = e && atoi(e) != 0;
+   e = getenv("PRIMME_AMD_CHEB_FUSED");
+   op->cheb_fused_all = e && atoi(e) != 0;
+   return 0;
+}
+
+/* Out = cx X + cw F G (+ cy Yk + cp Yprev) for nc columns, F = A (rows: m-vectors) or A' : the one-pass kernel when `fuse`
+ * and the matrix has the form for it (*fuse is cleared when it has not), else the product into the side's product panel and
+ * hipk_cheb_update */
+static int svds_cheb_combine(primme_amd_svds_operator *op, void *stream, int side, int *fuse, int nc, const hipk_cheb_coef *cf,
+      const void *X, int64_t ldx, const void *G, int64_t ldg, const void *Yk, int64_t ldk, const void *Yp, int64_t ldp, void *Out, int64_t ldo) {
+   hipk_csr *Fm = side ? op->A : op->At;
+   const hipk_dtype dt = hipk_csr_dtype(op->A);
+   g_cheb_products += nc;
+   if (*fuse) {
+      const int rc = hipk_csr_cheb_step_gather(Fm, stream, nc, cf, X, ldx, G, ldg, Yk, ldk, Yp, ldp, Out, ldo);
+      if (rc == 0) g_cheb_fused += nc;
+      if (rc != 1) return rc;
+      *fuse = 0;
+   }
+   const size_t es = op_elem(dt);
+   if (op->cheb_wcols[side] < op->cheb_cols) {
+      if (op->cheb_w[side]) (void)hipFree(op->cheb_w[side]);
+      op->cheb_w[side] = NULL; op->cheb_wcols[side] = 0;
+      if (hipMalloc(&op->cheb_w[side], (size_t)op->cheb_ld[side] * es * op->cheb_cols) != hipSuccess) return -2;
+      op->cheb_wcols[side] = op->cheb_cols;
+   }
+   int rc = hipk_csr_matvec(Fm, stream, G, ldg, op->cheb_w[side], op->cheb_ld[side], nc);
+   if (!rc) rc = hipk_cheb_update(stream, dt, hipk_csr_nrows(Fm), nc, cf, X, ldx, op->cheb_w[side], op->cheb_ld[side], Yk, ldk, Yp, ldp, Out, ldo);
+   return rc;
+}
+
+/* p(M) x for nc <= HIPK_CHEB_MAXCOLS columns, M = A'A (side 0) or AA' (side 1).  out == NULL: the result stays in the side's
+ * panel number steps % 2 (its other panel and the other side's panel number steps % 2 are left alone) */
+static int svds_cheb_poly(primme_amd_svds_operator *op, void *stream, int side, int *fuse, int nc, const char *x, int64_t lx, char *out, int64_t ldo) {
+   hipk_csr *first = side ? op->At : op->A;
+   const hipk_dtype dt = hipk_csr_dtype(op->A);
+   const size_t es = op_elem(dt);
+   const int d = op->cheb_steps;
+   const int64_t ld = op->cheb_ld[side], ldz = op->cheb_ld[!side], rows = hipk_csr_nrows(side ? op->A : op->At);
+   char *P[2] = {(char *)op->cheb_p[side], (char *)op->cheb_p[side] + (size_t)ld * es * op->cheb_cols};
+   char *z = (char *)op->cheb_p[!side] + (size_t)((d + 1) % 2) * ldz * es * op->cheb_cols;
+   const double lo = op->cheb_lo, hi = op->cheb_hi, dl = 0.5 * (hi - lo), sigma = op->cheb_sigma, tb = 0.5 * (hi + lo) - sigma;
+   double rho[HIPK_CHEB_MAXCOLS];
+   hipk_cheb_coef cf;
+   memset(&cf, 0, sizeof(cf));
+   for (int c = 0; c < nc; c++) { rho[c] = dl / tb; cf.cx[c] = 1.0 / tb; }
+   if (!out) { out = P[d % 2]; ldo = ld; }
+   if (d == 1) return hipk_cheb_update(stream, dt, rows, nc, &cf, x, lx, NULL, 0, NULL, 0, NULL, 0, out, ldo);
+   for (int k = 1; k < d; k++) {
+      for (int c = 0; c < nc; c++) cheb_step_coef(tb, dl, sigma, k, &rho[c], &cf, c);
+      /* as in primme_amd_chebyshev_precond: y_1 = x / tb is never stored, y_{k+1} goes over y_{k-1}, the last one to `out` */
+      const char *yk = k == 1 ? x : P[k % 2], *yp = k == 1 ? NULL : (k == 2 ? x : P[(k + 1) % 2]);
+      const int64_t ldk = k == 1 ? lx : ld, ldp = k == 2 ? lx : ld;
+      char *o = k == d - 1 ? out : P[(k + 1) % 2];
+      const int64_t lo_ = k == d - 1 ? ldo : ld;
+      int rc = hipk_csr_matvec(first, stream, yk, ldk, z, ldz, nc);
+      g_cheb_products += nc;
+      if (!rc) rc = svds_cheb_combine(op, stream, side, fuse, nc, &cf, x, lx, z, ldz, yk, ldk, yp, ldp, o, lo_);
+      if (rc) return rc;
+   }
+   return 0;
+}
+
+extern "C" void primme_amd_svds_chebyshev_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy, int *blockSize,
+      int *mode, struct primme_svds_params *ps, int *ierr) {
+   primme_amd_svds_operator *op = (primme_amd_svds_operator *)ps->preconditioner;
+   *ierr = 1;
+   if (!op || op->comm || op->cheb_steps < 1) return;
+   if (*mode != primme_svds_op_AtA && *mode != primme_svds_op_AAt && *mode != primme_svds_op_augmented) return;
+   if (*blockSize <= 0) { *ierr = 0; return; }
+   void *stream = ps->queue ? (void *)*(hipStream_t *)ps->queue : NULL;
+   if (!stream) stream = hipk_ctx_stream(hipk_csr_ctx(op->A));
+   const hipk_dtype dt = hipk_csr_dtype(op->A);
+   const size_t es = op_elem(dt);
+   /* vector lengths from the matrices: for the real-equivalent form of a complex matrix they are the 2n / 2m real rows, and the
+    * leading dimensions, which arrive in complex elements, double (the recurrence has real coefficients) */
+   const int64_t len[2] = {hipk_csr_nrows(op->At), hipk_csr_nrows(op->A)};
+   const int64_t f = op->cplx ? 2 : 1, lx = f * *ldx, ly = f * *ldy;
+   const int d = op->cheb_steps;
+   const int want = *blockSize < HIPK_CHEB_MAXCOLS ? *blockSize : HIPK_CHEB_MAXCOLS;
+   if (want > op->cheb_cols) {
+      for (int i = 0; i < 2; i++) {
+         if (op->cheb_p[i]) (void)hipFree(op->cheb_p[i]);
+         if (op->cheb_w[i]) (void)hipFree(op->cheb_w[i]);
+         op->cheb_p[i] = op->cheb_w[i] = NULL; op->cheb_wcols[i] = 0;
+      }
+      op->cheb_cols = 0;
+      for (int i = 0; i < 2; i++) {
+         op->cheb_ld[i] = (len[i] + 3) / 4 * 4 + 4;           /* columns on 16-byte boundaries */
+         if (hipMalloc(&op->cheb_p[i], (size_t)op->cheb_ld[i] * es * 2 * want) != hipSuccess) return;
+      }
+      op->cheb_cols = want;
+   }
+   int fuse = !op->cheb_unfused;
+   int rc = 0;
+   for (int c0 = 0; c0 < *blockSize && !rc; c0 += HIPK_CHEB_MAXCOLS) {
+      const int nc = *blockSize - c0 < HIPK_CHEB_MAXCOLS ? *blockSize - c0 : HIPK_CHEB_MAXCOLS;
+      const char *xc = (const char *)x + (size_t)c0 * lx * es;
+      char *yc = (char *)y + (size_t)c0 * ly * es;
+      int fz = fuse && (op->cheb_fused_all || nc <= CHEB_FUSE_GATHER_MAXCOLS);
+      g_cheb_applies += nc;
+      if (*mode != primme_svds_op_augmented) {
+         rc = svds_cheb_poly(op, stream, *mode == primme_svds_op_AAt, &fz, nc, xc, lx, yc, ly);
+      } else {
+         /* t_v = p(A'A) v and t_u = p(AA') u into panel d % 2 of either side, then [y_v; y_u] = [sshift t_v + A' t_u; sshift t_u + A t_v] */
+         const size_t uoff = (size_t)len[0] * es;
+         rc = svds_cheb_poly(op, stream, 0, &fz, nc, xc, lx, NULL, 0);
+         if (!rc) rc = svds_cheb_poly(op, stream, 1, &fz, nc, xc + uoff, lx, NULL, 0);
+         const char *tv = (const char *)op->cheb_p[0] + (size_t)(d % 2) * op->cheb_ld[0] * es * op->cheb_cols;
+         const char *tu = (const char *)op->cheb_p[1] + (size_t)(d % 2) * op->cheb_ld[1] * es * op->cheb_cols;
+         hipk_cheb_coef cf;
+         memset(&cf, 0, sizeof(cf));
+         for (int c = 0; c < nc; c++) { cf.cx[c] = op->cheb_sshift; cf.cw[c] = 1.0; }
+         if (!rc) rc = svds_cheb_combine(op, stream, 0, &fz, nc, &cf, tv, op->cheb_ld[0], tu, op->cheb_ld[1], NULL, 0, NULL, 0, yc, ly);
+         if (!rc) rc = svds_cheb_combine(op, stream, 1, &fz, nc, &cf, tu, op->cheb_ld[1], tv, op->cheb_ld[0], NULL, 0, NULL, 0, yc + uoff, ly);
+      }
+      if (fuse && (op->cheb_fused_all || nc <= CHEB_FUSE_GATHER_MAXCOLS) && !fz) fuse = 0;   /* no one-pass form for these matrices */
    }
    *ierr = rc ? 1 : 0;
 }

@@ -173,3 +173,54 @@ int hipk_cheb_gershgorin_rows(hipk_ctx *ctx, hipStream_t st, hipk_dtype dt, int6
    out[0] = res[0]; out[1] = res[1];
    return 0;
 }
+
+/* ---- largest absolute row sum of a CSR slab ---------------------------------------------------------------------
+ * part[b] = max over the rows of workgroup b of sum_j |a_ij| (one lane per row, the entries added in row order in double);
+ * the second stage folds the partial maxima in a fixed order.  A maximum does not depend on the order anyway: the result is
+ * the same on every grid. */
+template <typename T>
+__global__ void __launch_bounds__(HIPK_BLOCK)
+cheb_abs_rowsum_kernel(int64_t nrows, const int32_t *__restrict__ rowptr, const T *__restrict__ val, double *__restrict__ part) {
+   __shared__ double smax[HIPK_BLOCK / HIPK_WAVE];
+   double hi = 0.0;
+   const int64_t stride = (int64_t)gridDim.x * HIPK_BLOCK;
+   for (int64_t i = (int64_t)blockIdx.x * HIPK_BLOCK + threadIdx.x; i < nrows; i += stride) {
+      double s = 0.0;
+      for (int32_t q = rowptr[i]; q < rowptr[i + 1]; q++) s += fabs((double)val[q]);
+      hi = fmax(hi, s);
+   }
+   for (int o = 32; o > 0; o >>= 1) hi = fmax(hi, __shfl_xor(hi, o));
+   if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = hi;
+   __syncthreads();
+   if (threadIdx.x == 0) part[blockIdx.x] = fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]));
+}
+__global__ void __launch_bounds__(HIPK_BLOCK)
+cheb_max_kernel(const double *__restrict__ part, int nb, double *__restrict__ out) {
+   __shared__ double smax[HIPK_BLOCK / HIPK_WAVE];
+   double hi = 0.0;
+   for (int b = threadIdx.x; b < nb; b += HIPK_BLOCK) hi = fmax(hi, part[b]);
+   for (int o = 32; o > 0; o >>= 1) hi = fmax(hi, __shfl_xor(hi, o));
+   if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = hi;
+   __syncthreads();
+   if (threadIdx.x == 0) out[0] = fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]));
+}
+
+/* library-internal (hipk_csr_abs_rowsum_max in hipk_sparse.hip owns the matrix); complete on return, 0 for an empty slab */
+int hipk_cheb_abs_rowsum_rows(hipk_ctx *ctx, hipStream_t st, hipk_dtype dt, int64_t nrows, const int32_t *rowptr, const void *val, double *out) {
+   *out = 0.0;
+   if (nrows <= 0) return 0;
+   const int gx = hipk_grid_for_rows(ctx, nrows, HIPK_BLOCK, 8);
+   double *part = NULL;
+   HIPK_CHECK(hipMalloc((void **)&part, sizeof(double) * ((size_t)gx + 1)));
+   if (dt == HIPK_F64) hipLaunchKernelGGL(cheb_abs_rowsum_kernel<double>, dim3(gx), dim3(HIPK_BLOCK), 0, st, nrows, rowptr, (const double *)val, part);
+   else hipLaunchKernelGGL(cheb_abs_rowsum_kernel<float>, dim3(gx), dim3(HIPK_BLOCK), 0, st, nrows, rowptr, (const float *)val, part);
+   hipLaunchKernelGGL(cheb_max_kernel, dim3(1), dim3(HIPK_BLOCK), 0, st, part, gx, part + gx);
+   hipError_t e = hipGetLastError();
+   if (e == hipSuccess) e = hipStreamSynchronize(st);
+   double res = 0.0;
+   const int rc = e == hipSuccess ? hipk_download(ctx, &res, part + gx, sizeof(res)) : -1;
+   (void)hipFree(part);
+   if (e != hipSuccess || rc) { fprintf(stderr, "primme_amd: row-sum reduction failed: %s\n", e != hipSuccess ? hipGetErrorString(e) : "read-back"); return -1; }
+   *out = res;
+   return 0;
+}

@@ -61,6 +61,7 @@ extern "C" int hipk_pat_enabled(void);
 extern "C" int hipk_pat_cheb_step(const hipk_pat *B, void *hip_stream, int gx, const double cf[4], const void *xr, const void *yk, const void *yp, void *out);
 int hipk_cheb_gershgorin_rows(hipk_ctx *ctx, hipStream_t st, hipk_dtype dt, int64_t nrows, int64_t row0, const int32_t *rowptr,
       const int32_t *colind, const void *val, double out[2]);
+int hipk_cheb_abs_rowsum_rows(hipk_ctx *ctx, hipStream_t st, hipk_dtype dt, int64_t nrows, const int32_t *rowptr, const void *val, double *out);
 extern "C" int hipk_pb_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t n, const int32_t *rp, const int32_t *ci, const void *val, hipk_pb **out);
 extern "C" int hipk_pb_matvec(const hipk_pb *B, void *hip_stream, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols);
 extern "C" void hipk_pb_destroy(hipk_pb *B);
@@ -327,23 +328,36 @@ csr_rows_block_kernel(const int32_t *__restrict__ tiles, int ntiles, const int32
 #define XS_MAX 3072
 #define XS_SMALL 1728      /* 192 window rows of 8 columns on the odd stride of 9: 39 KB of LDS per workgroup, still 4 per CU (1536 until round 6) */
 struct SpmmShift { double s[64]; int on; int nosplit; int evenstride; };
-/* CHEB: the row sums are not stored but combined with the row's own entries of three panels — one step of the Chebyshev
- * recurrence (hipk_cheb.hip): y(i,c) = cy[c] x(i,c) + cp[c] yp(i,c) + cx[c] xr(i,c) + cw[c] (A x)(i,c), x being the iterate
- * the product gathers from (yp == NULL: no such term).  y may be yp (row-local), never x. */
-template <typename T> struct SpmmCheb { hipk_cheb_coef cf; const T *xr; int64_t ldr; const T *yp; int64_t ldp; };
+/* CHEB: the row sums are not stored but combined with the row's own entries of up to three panels — one step of the Chebyshev
+ * recurrence (hipk_cheb.hip): y(i,c) = cy[c] yk(i,c) + cp[c] yp(i,c) + cx[c] xr(i,c) + cw[c] (A x)(i,c).  Square operators
+ * (hipk_csr_cheb_step): yk is x, the iterate the product gathers from.  Rectangular ones (hipk_csr_cheb_step_gather): x has
+ * ncols(A) rows and is only gathered, yk is a panel of its own or NULL; yp == NULL: no such term.  y may be yk or yp (row-local),
+ * never x.  seq: the row sum of a one-column call is formed as csr_stream_kernel forms it (every product rounded, then added in
+ * row order, one lane per row), so that the step equals that kernel followed by cheb_update_kernel bit for bit. */
+template <typename T> struct SpmmCheb { hipk_cheb_coef cf; const T *xr; int64_t ldr; const T *yp; int64_t ldp; const T *yk; int64_t ldk; int seq; };
 struct SpmmNoEp {};
 template <typename T, bool CHEB> struct SpmmEp { typedef SpmmNoEp type; };
 template <typename T> struct SpmmEp<T, true> { typedef SpmmCheb<T> type; };
 template <typename T, bool CHEB>
-__device__ __forceinline__ double spmm_epilogue(const typename SpmmEp<T, CHEB>::type &ep, double sum, const T *__restrict__ x, int64_t ldx, int64_t row, int c) {
+__device__ __forceinline__ double spmm_epilogue(const typename SpmmEp<T, CHEB>::type &ep, double sum, int64_t row, int c) {
    if constexpr (CHEB) {
       double o = ep.cf.cx[c] * (double)ep.xr[row + (size_t)c * ep.ldr];
-      o = fma(ep.cf.cy[c], (double)x[row + (size_t)c * ldx], o);
+      if (ep.yk) o = fma(ep.cf.cy[c], (double)ep.yk[row + (size_t)c * ep.ldk], o);
       if (ep.yp) o = fma(ep.cf.cp[c], (double)ep.yp[row + (size_t)c * ep.ldp], o);
       return fma(ep.cf.cw[c], sum, o);
    } else {
       return sum;
    }
+}
+template <typename T, bool CHEB>
+__device__ __forceinline__ bool spmm_seq(const typename SpmmEp<T, CHEB>::type &ep) {
+   if constexpr (CHEB) return ep.seq > 0; else return false;
+}
+/* acc + round(v x): two roundings, never contracted into one fma */
+__device__ __forceinline__ double spmm_add_rounded_product(double acc, double v, double x) {
+#pragma clang fp contract(off)
+   const double p = v * x;
+   return acc + p;
 }
 template <typename T, int NC, int XS, bool C16, bool CHEB = false>
 __global__ void __launch_bounds__(HIPK_BLOCK)
@@ -415,7 +429,8 @@ csr_window_block_kernel(const int4 *__restrict__ tileinfo, const int2 *__restric
       /* A tile of 2048 nonzeros has ~120 rows of 17: with one lane per (row, column group) half of the workgroup idles
        * through the row walk, a chain of dependent LDS reads.  When the work fits twice, two adjacent lanes share a row:
        * each walks half of its nonzeros and the halves meet in a shuffle (fixed order: low half + high half). */
-      const int split = (2 * nr * ngroups <= HIPK_BLOCK && !sh.nosplit) ? 2 : 1;
+      const bool seq = spmm_seq<T, CHEB>(ep);
+      const int split = (2 * nr * ngroups <= HIPK_BLOCK && !sh.nosplit && !seq) ? 2 : 1;
       for (int idx0 = threadIdx.x; idx0 < nr * ngroups * split; idx0 += HIPK_BLOCK) {
          const int idx = idx0 / split, half = idx0 - idx * split;
          const int g = idx / nr, r = idx - g * nr, c0 = g * NC;
@@ -424,7 +439,12 @@ csr_window_block_kernel(const int4 *__restrict__ tileinfo, const int2 *__restric
          for (int c = 0; c < NC; c++) acc[c] = 0.0;
          int qa = rp[r], qb = rp[r + 1];
          if (split == 2) { const int qm = qa + (qb - qa + 1) / 2; if (half) qa = qm; else qb = qm; }
-         if (win) {
+         if (seq) {
+            /* one column (c0 = 0, the lane's other accumulators stay 0): csr_stream_kernel's order and roundings */
+            const T *xg = x - row0;
+            if (win) for (int q = qa; q < qb; q++) acc[0] = spmm_add_rounded_product(acc[0], (double)sval[q], xs[scol[q] * xst]);
+            else for (int q = qa; q < qb; q++) acc[0] = spmm_add_rounded_product(acc[0], (double)sval[q], (double)xg[(int64_t)scol[q]]);
+         } else if (win) {
             int cofs[NC];
 #pragma unroll
             for (int c = 0; c < NC; c++) cofs[c] = (c0 + c < ncols) ? c0 + c : ncols - 1;
@@ -465,7 +485,7 @@ csr_window_block_kernel(const int4 *__restrict__ tileinfo, const int2 *__restric
             if (c0 + c < ncols) {
                double out = acc[c];
                if (sh.on) out = fma(-sh.s[c0 + c], (double)x[(int64_t)(r0 + r) + (size_t)(c0 + c) * ldx], out);
-               out = spmm_epilogue<T, CHEB>(ep, out, x, ldx, (int64_t)(r0 + r), c0 + c);
+               out = spmm_epilogue<T, CHEB>(ep, out, (int64_t)(r0 + r), c0 + c);
                y[r0 + r + (size_t)(c0 + c) * ldy] = (T)out;
             }
       }
@@ -483,7 +503,7 @@ csr_window_block_kernel(const int4 *__restrict__ tileinfo, const int2 *__restric
             if (threadIdx.x == 0) {
                double out = (red[0] + red[1]) + (red[2] + red[3]);
                if (sh.on) out = fma(-sh.s[c], (double)xc[row0 + r], out);
-               out = spmm_epilogue<T, CHEB>(ep, out, x, ldx, (int64_t)r, c);
+               out = spmm_epilogue<T, CHEB>(ep, out, (int64_t)r, c);
                y[r + (size_t)c * ldy] = (T)out;
             }
             __syncthreads();
@@ -831,7 +851,7 @@ static int csr_matvec_t(hipk_csr *A, hipStream_t stream, const T *x, int64_t ldx
       else if (one_pb) streamed = hipk_pb_bytes(A->pb) * ncols;
       else streamed = (double)A->nnz * (es + ((win || ncols == 1) && csr16(A) ? 2 : 4)) + (A->nrows + 1) * 4.0 + 2.0 * A->nrows * es * ncols;
    }
-   if (cheb) streamed += (cheb->yp ? 2.0 : 1.0) * A->nrows * es * ncols;      /* the epilogue's two other panels */
+   if (cheb) streamed += ((cheb->yp ? 2.0 : 1.0) + (cheb->yk && cheb->yk != x ? 1.0 : 0.0)) * A->nrows * es * ncols;      /* the epilogue's other panels */
    const int pslot = hipk_prof_begin_s(HIPK_PROF_SPMV, stream, cheb ? streamed : alg, streamed);
    if (A->pat && hipk_pat_enabled() && ncols == 1 && !shift_host && !cheb) {
       const int rc = hipk_pat_matvec(A->pat, stream, hipk_pat_grid(A->pat, ctx->num_cu), x, y, A->halo_lo, A->halo_hi, A->xlo, A->xhi, NULL, 0, NULL,
@@ -864,7 +884,7 @@ static int csr_matvec_t(hipk_csr *A, hipStream_t stream, const T *x, int64_t ldx
          sh.on = shift_host != NULL;
          static int nosplit = -1;                   /* HIPK_SPMM_NO_SPLIT=1: one lane per row always (A/B knob) */
          if (nosplit < 0) nosplit = getenv("HIPK_SPMM_NO_SPLIT") != NULL;
-         sh.nosplit = nosplit;
+         sh.nosplit = nosplit || (cheb && cheb->seq < 0);
          static int evenstride = -1;                /* HIPK_SPMM_EVEN_STRIDE=1: window rows ncols apart in LDS, as until round 5 (A/B knob) */
          if (evenstride < 0) evenstride = getenv("HIPK_SPMM_EVEN_STRIDE") != NULL;
          sh.evenstride = evenstride;
@@ -970,11 +990,41 @@ extern "C" int hipk_csr_cheb_step(hipk_csr *A, void *hip_stream, int nx, const h
       return 0;
    }
    if (A->dt == HIPK_F64) {
-      const SpmmCheb<double> ep = {*coef, (const double *)X, ldx, (const double *)Yprev, ldp};
+      const SpmmCheb<double> ep = {*coef, (const double *)X, ldx, (const double *)Yprev, ldp, (const double *)Yk, ldk, 0};
       return csr_matvec_t<double>(A, st, (const double *)Yk, ldk, (double *)Out, ldo, nx, NULL, &ep);
    }
-   const SpmmCheb<float> ep = {*coef, (const float *)X, ldx, (const float *)Yprev, ldp};
+   const SpmmCheb<float> ep = {*coef, (const float *)X, ldx, (const float *)Yprev, ldp, (const float *)Yk, ldk, 0};
    return csr_matvec_t<float>(A, st, (const float *)Yk, ldk, (float *)Out, ldo, nx, NULL, &ep);
+}
+
+/* The same step for a RECTANGULAR operator (include/primme_amd_kernels.h): Out = cy Yk + cp Yprev + cx X + cw A G, G the only
+ * gathered panel (ncols(A) rows), everything else row-local.  One launch of the windowed block kernel for all columns.  The row
+ * sum is formed as hipk_csr_matvec forms it for the same matrix and width, so that in double the step equals that product
+ * followed by hipk_cheb_update bit for bit: one column: csr_stream_kernel's rounded products (seq = 1); more columns:
+ * this very kernel when the matrix is windowed, else csr_rows_block_kernel's fma chain without the two-lane split (seq = -1).
+ * 1 = no row-tile form (panel-blocked, row patterns, stencil, halo, complex): the caller runs the generic pair. */
+extern "C" int hipk_csr_cheb_step_gather(hipk_csr *A, void *hip_stream, int nx, const hipk_cheb_coef *coef, const void *X, int64_t ldx,
+      const void *G, int64_t ldg, const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp, void *Out, int64_t ldo) {
+   if (!A) return -1;
+   if (A->kind != 0 || hipk_csr_format(A) != 0 || A->halo_lo != 0 || A->halo_hi != 0 || HIPK_IS_Z(A->dt)) return 1;
+   if (nx <= 0 || A->nrows == 0) return 0;
+   if (nx > HIPK_CHEB_MAXCOLS || !coef || !X || !G || !Out || Out == G) return -1;
+   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : A->ctx->stream;
+   const int seq = nx == 1 ? 1 : (A->windowed ? 0 : -1);
+   if (A->dt == HIPK_F64) {
+      const SpmmCheb<double> ep = {*coef, (const double *)X, ldx, (const double *)Yprev, ldp, (const double *)Yk, ldk, seq};
+      return csr_matvec_t<double>(A, st, (const double *)G, ldg, (double *)Out, ldo, nx, NULL, &ep);
+   }
+   const SpmmCheb<float> ep = {*coef, (const float *)X, ldx, (const float *)Yprev, ldp, (const float *)Yk, ldk, seq};
+   return csr_matvec_t<float>(A, st, (const float *)G, ldg, (float *)Out, ldo, nx, NULL, &ep);
+}
+
+/* max_i sum_j |a_ij| over the local rows: the infinity norm of the slab (of A' : the 1-norm of A) */
+extern "C" int hipk_csr_abs_rowsum_max(hipk_csr *A, void *hip_stream, double *out) {
+   if (!A || !out) return -1;
+   if (A->kind != 0 || (A->dt != HIPK_F64 && A->dt != HIPK_F32)) return -44;
+   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : A->ctx->stream;
+   return hipk_cheb_abs_rowsum_rows(A->ctx, st, A->dt, A->nrows, A->rowptr, A->values, out);
 }
 
 /* Gershgorin bounds of the local rows (include/primme_amd_kernels.h).  The Laplacian stencil form has diagonal 2 d and 2 d
