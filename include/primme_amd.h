@@ -170,6 +170,40 @@ typedef enum {
    PRIMME_LOBPCG_OrthoBasis, PRIMME_LOBPCG_OrthoBasis_Window
 } primme_preset_method;
 
+/* ---- access to the members by label or by name: what the bindings of the reference and its Fortran layer are written on
+ *      (reference include/primme_eigs.h:279-378; the numeric values are ABI, bindings pass them as integers) ---------------- */
+typedef enum { primme_int = 0, primme_double, primme_pointer, primme_string } primme_type;
+
+typedef enum {
+   PRIMME_invalid_label = 0,
+   PRIMME_n = 1, PRIMME_matrixMatvec = 2, PRIMME_matrixMatvec_type = 3, PRIMME_applyPreconditioner = 4,
+   PRIMME_applyPreconditioner_type = 5, PRIMME_massMatrixMatvec = 6, PRIMME_massMatrixMatvec_type = 7, PRIMME_numProcs = 8,
+   PRIMME_procID = 9, PRIMME_commInfo = 10, PRIMME_nLocal = 11, PRIMME_globalSumReal = 12, PRIMME_globalSumReal_type = 13,
+   PRIMME_broadcastReal = 14, PRIMME_broadcastReal_type = 15, PRIMME_numEvals = 16, PRIMME_target = 17,
+   PRIMME_numTargetShifts = 18, PRIMME_targetShifts = 19, PRIMME_locking = 20, PRIMME_initSize = 21,
+   PRIMME_numOrthoConst = 22, PRIMME_maxBasisSize = 23, PRIMME_minRestartSize = 24, PRIMME_maxBlockSize = 25,
+   PRIMME_maxMatvecs = 26, PRIMME_maxOuterIterations = 27, PRIMME_iseed = 28, PRIMME_aNorm = 29, PRIMME_BNorm = 30,
+   PRIMME_invBNorm = 31, PRIMME_eps = 32, PRIMME_orth = 33, PRIMME_internalPrecision = 34, PRIMME_printLevel = 35,
+   PRIMME_outputFile = 36, PRIMME_matrix = 37, PRIMME_massMatrix = 38, PRIMME_preconditioner = 39,
+   PRIMME_ShiftsForPreconditioner = 40, PRIMME_initBasisMode = 41, PRIMME_projectionParams_projection = 42,
+   PRIMME_restartingParams_maxPrevRetain = 43, PRIMME_correctionParams_precondition = 44,
+   PRIMME_correctionParams_robustShifts = 45, PRIMME_correctionParams_maxInnerIterations = 46,
+   PRIMME_correctionParams_projectors_LeftQ = 47, PRIMME_correctionParams_projectors_LeftX = 48,
+   PRIMME_correctionParams_projectors_RightQ = 49, PRIMME_correctionParams_projectors_RightX = 50,
+   PRIMME_correctionParams_projectors_SkewQ = 51, PRIMME_correctionParams_projectors_SkewX = 52,
+   PRIMME_correctionParams_convTest = 53, PRIMME_correctionParams_relTolBase = 54, PRIMME_stats_numOuterIterations = 55,
+   PRIMME_stats_numRestarts = 56, PRIMME_stats_numMatvecs = 57, PRIMME_stats_numPreconds = 58,
+   PRIMME_stats_numGlobalSum = 59, PRIMME_stats_volumeGlobalSum = 60, PRIMME_stats_numBroadcast = 61,
+   PRIMME_stats_volumeBroadcast = 62, PRIMME_stats_flopsDense = 63, PRIMME_stats_numOrthoInnerProds = 64,
+   PRIMME_stats_elapsedTime = 65, PRIMME_stats_timeMatvec = 66, PRIMME_stats_timePrecond = 67, PRIMME_stats_timeOrtho = 68,
+   PRIMME_stats_timeGlobalSum = 69, PRIMME_stats_timeBroadcast = 70, PRIMME_stats_timeDense = 71,
+   PRIMME_stats_estimateMinEVal = 72, PRIMME_stats_estimateMaxEVal = 73, PRIMME_stats_estimateLargestSVal = 74,
+   PRIMME_stats_estimateBNorm = 75, PRIMME_stats_estimateInvBNorm = 76, PRIMME_stats_maxConvTol = 77,
+   PRIMME_stats_lockingIssue = 78, PRIMME_dynamicMethodSwitch = 79, PRIMME_convTestFun = 80, PRIMME_convTestFun_type = 81,
+   PRIMME_convtest = 82, PRIMME_ldevecs = 83, PRIMME_ldOPs = 84, PRIMME_monitorFun = 85, PRIMME_monitorFun_type = 86,
+   PRIMME_monitor = 87, PRIMME_queue = 88, PRIMME_profile = 89
+} primme_params_label;
+
 /* convergence flags reported to monitorFun (reference src/eigs/common_eigs.h:41-46) */
 enum primme_amd_conv_flags {
    PRIMME_AMD_UNCONVERGED = 0, PRIMME_AMD_SKIP_UNTIL_RESTART, PRIMME_AMD_CONVERGED,
@@ -184,6 +218,29 @@ void primme_set_defaults(primme_params *primme);
 void primme_free(primme_params *primme);
 primme_params *primme_params_create(void);
 int  primme_params_destroy(primme_params *primme);
+
+/* Prints the configuration to primme.outputFile, in the reference's format character for character (the block is passed
+ * by value, reference src/eigs/primme_interface.c:629). */
+void primme_display_params(primme_params primme);
+/* Members by label.  `value` is, by the member's kind (primme_member_info): primme_int -> PRIMME_INT* (iseed: 4 of them),
+ * primme_double with arity 1 -> double*; get stores through it, set reads through it.  For primme_pointer, primme_string and
+ * the arrays of arity 0 (targetShifts, ShiftsForPreconditioner) set takes the pointer to store AS `value` and get stores the
+ * member through (void **)value.  Return 0, or 1 for an unknown label, a value above INT_MAX for an int member, or a member
+ * the reference does not serve: get of globalSumReal_type / broadcastReal_type, set of stats_numGlobalSum /
+ * stats_numBroadcast.  Those two *_type labels have no name either: primme_member_info returns 1 for them. */
+int primme_get_member(primme_params *primme, primme_params_label label, void *value);
+int primme_set_member(primme_params *primme, primme_params_label label, void *value);
+/* Looks a member up by *label, or by *label_name when that is given and matches (names join the nested structures with '_'
+ * and drop "Params": correction_maxInnerIterations); fills in the other of the two, the kind and the arity.  Any of the
+ * pointers may be NULL except both of label and label_name.  Returns 0, or 1 when nothing matches. */
+int primme_member_info(primme_params_label *label, const char **label_name, primme_type *type, int *arity);
+/* The value of an enumerator given by name ("primme_proj_refined", "PRIMME_JDQMR"); 0, or 1 for an unknown name. */
+int primme_constant_info(const char *label_name, int *value);
+/* Enumerators of the member `label`: *value >= 0 and *value_name == NULL asks for the name, *value < 0 and a name asks for the
+ * value.  0; -1 for any other combination; -2 when not found or the member is not of an enumeration the reference lists
+ * (it lists target, projection, initBasisMode, convTest, orth and five of the *_type members; the preset methods answer
+ * to the label PRIMME_commInfo). */
+int primme_enum_member_info(primme_params_label label, int *value, const char **value_name);
 
 /* Solvers: same contract as the reference's cublas_?primme / magma_?primme
  * (reference include/primme_eigs.h:394-417, src/eigs/primme_c.c:103-108):

@@ -89,6 +89,29 @@ typedef struct primme_svds_params {
    const char *profile;
 } primme_svds_params;
 
+/* labels of the members (reference include/primme_svds.h:166-230); the numeric values are ABI */
+typedef enum {
+   PRIMME_SVDS_invalid_label = 0,
+   PRIMME_SVDS_primme = 1, PRIMME_SVDS_primmeStage2 = 2, PRIMME_SVDS_m = 3, PRIMME_SVDS_n = 4, PRIMME_SVDS_matrixMatvec = 5,
+   PRIMME_SVDS_matrixMatvec_type = 6, PRIMME_SVDS_applyPreconditioner = 7, PRIMME_SVDS_applyPreconditioner_type = 8,
+   PRIMME_SVDS_numProcs = 9, PRIMME_SVDS_procID = 10, PRIMME_SVDS_mLocal = 11, PRIMME_SVDS_nLocal = 12,
+   PRIMME_SVDS_commInfo = 13, PRIMME_SVDS_globalSumReal = 14, PRIMME_SVDS_globalSumReal_type = 15,
+   PRIMME_SVDS_broadcastReal = 16, PRIMME_SVDS_broadcastReal_type = 17, PRIMME_SVDS_numSvals = 18, PRIMME_SVDS_target = 19,
+   PRIMME_SVDS_numTargetShifts = 20, PRIMME_SVDS_targetShifts = 21, PRIMME_SVDS_method = 22, PRIMME_SVDS_methodStage2 = 23,
+   PRIMME_SVDS_matrix = 24, PRIMME_SVDS_preconditioner = 25, PRIMME_SVDS_locking = 26, PRIMME_SVDS_numOrthoConst = 27,
+   PRIMME_SVDS_aNorm = 28, PRIMME_SVDS_eps = 29, PRIMME_SVDS_precondition = 30, PRIMME_SVDS_initSize = 31,
+   PRIMME_SVDS_maxBasisSize = 32, PRIMME_SVDS_maxBlockSize = 33, PRIMME_SVDS_maxMatvecs = 34, PRIMME_SVDS_iseed = 35,
+   PRIMME_SVDS_printLevel = 36, PRIMME_SVDS_internalPrecision = 37, PRIMME_SVDS_outputFile = 38,
+   PRIMME_SVDS_stats_numOuterIterations = 39, PRIMME_SVDS_stats_numRestarts = 40, PRIMME_SVDS_stats_numMatvecs = 41,
+   PRIMME_SVDS_stats_numPreconds = 42, PRIMME_SVDS_stats_numGlobalSum = 43, PRIMME_SVDS_stats_volumeGlobalSum = 44,
+   PRIMME_SVDS_stats_numBroadcast = 45, PRIMME_SVDS_stats_volumeBroadcast = 46, PRIMME_SVDS_stats_numOrthoInnerProds = 47,
+   PRIMME_SVDS_stats_elapsedTime = 48, PRIMME_SVDS_stats_timeMatvec = 49, PRIMME_SVDS_stats_timePrecond = 50,
+   PRIMME_SVDS_stats_timeOrtho = 51, PRIMME_SVDS_stats_timeGlobalSum = 52, PRIMME_SVDS_stats_timeBroadcast = 53,
+   PRIMME_SVDS_stats_lockingIssue = 54, PRIMME_SVDS_convTestFun = 55, PRIMME_SVDS_convTestFun_type = 56,
+   PRIMME_SVDS_convtest = 57, PRIMME_SVDS_monitorFun = 58, PRIMME_SVDS_monitorFun_type = 59, PRIMME_SVDS_monitor = 60,
+   PRIMME_SVDS_queue = 61, PRIMME_SVDS_profile = 62
+} primme_svds_params_label;
+
 primme_svds_params *primme_svds_params_create(void);
 int primme_svds_params_destroy(primme_svds_params *primme_svds);
 void primme_svds_initialize(primme_svds_params *primme_svds);
@@ -96,6 +119,21 @@ int primme_svds_set_method(primme_svds_preset_method method, primme_preset_metho
       primme_preset_method methodStage2, primme_svds_params *primme_svds);
 void primme_svds_set_defaults(primme_svds_params *primme_svds);
 void primme_svds_free(primme_svds_params *primme_svds);
+
+/* Prints the configuration to primme_svds.outputFile in the reference's format (src/svds/primme_svds_interface.c:421): the
+ * block itself, then primme_svds.primme under the prefix "primme" when method is set and primme_svds.primmeStage2 under
+ * "primmeStage2" when methodStage2 is. */
+void primme_svds_display_params(primme_svds_params primme_svds);
+/* The member interface of primme_amd.h for primme_svds_params, with the same conventions for `value`.  The labels primme and
+ * primmeStage2 are pointers that can be read (the address of the nested block, to be used with primme_get_member /
+ * primme_set_member) and not set; stats_numGlobalSum, stats_numBroadcast and stats_lockingIssue cannot be set either.
+ * iseed is reported with arity 1 although get and set move four values.  primme_svds_constant_info also knows every name of
+ * primme_constant_info; in primme_svds_enum_member_info the preset methods answer to PRIMME_SVDS_commInfo. */
+int primme_svds_get_member(primme_svds_params *primme_svds, primme_svds_params_label label, void *value);
+int primme_svds_set_member(primme_svds_params *primme_svds, primme_svds_params_label label, void *value);
+int primme_svds_member_info(primme_svds_params_label *label, const char **label_name, primme_type *type, int *arity);
+int primme_svds_constant_info(const char *label_name, int *value);
+int primme_svds_enum_member_info(primme_svds_params_label label, int *value, const char **value_name);
 
 /* svecs: DEVICE array [U (mLocal x numSvals, ld mLocal) | V (nLocal x numSvals, ld nLocal)] behind
  * numOrthoConst constraint columns of each; svals, resNorms: host arrays.  The user matvec gets

@@ -190,6 +190,19 @@ def declare_solver(lib, prefix):
             f.restype = C.c_int
 
 
+def declare_members(lib):
+    """members by label / name and the configuration listing (include/primme_amd.h, primme_amd_svds.h)"""
+    P = C.POINTER
+    for pre, params in (("primme_", PrimmeParams), ("primme_svds_", PrimmeSvdsParams)):
+        for name, args in (("get_member", [_vp, _i, _vp]), ("set_member", [_vp, _i, _vp]),
+                           ("member_info", [P(_i), P(C.c_char_p), P(_i), P(_i)]), ("constant_info", [C.c_char_p, P(_i)]),
+                           ("enum_member_info", [_i, P(_i), P(C.c_char_p)])):
+            f = getattr(lib, pre + name)
+            f.argtypes, f.restype = args, C.c_int
+        f = getattr(lib, pre + "display_params")
+        f.argtypes, f.restype = [params], None      # the block travels by value
+
+
 def declare_kernels(lib):
     P = C.POINTER
     sig = {

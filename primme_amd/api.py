@@ -12,6 +12,7 @@ import hashlib
 import numpy as np
 
 from . import _ffi as F
+from .members import apply_members
 
 
 class Operator:
@@ -180,7 +181,7 @@ class Session:
               maxMatvecs=0, maxOuterIterations=0, targetShifts=None, precond=None, printLevel=0,
               initBasisMode=None, global_sum=None, numProcs=1, procID=0, orth=None, iseed=None,
               profile=False, return_evecs=True, monitor=None, user_matvec=None, projection=None,
-              constraints=None, user_precond=None, tweak=None):
+              constraints=None, user_precond=None, tweak=None, members=None):
         lib, op, dtype = self.lib, self.op, self.dtype
         keep = []
         cheb = isinstance(precond, (tuple, list)) and len(precond) > 0 and precond[0] == "chebyshev"
@@ -322,6 +323,8 @@ class Session:
 
         if lib.primme_set_method(m, C.byref(p)):
             raise ValueError("unknown method")
+        if members:                      # {"dotted.name": value}: members by name through primme_set_member (members.py)
+            apply_members(lib, p, members, keep)
         if tweak is not None:            # last word on the parameter structure (e.g. the correction equation's projectors)
             tweak(p)
         evals = np.zeros(numEvals, dtype=self.rdtype)
@@ -347,6 +350,9 @@ def eigsh(op, backend="hip", comm=None, dtype=np.float64, complex_form="native",
     precond: None | "jacobi" (Davidson: per-vector shifts) | ("jacobi", shift) (fixed shift) |
     ("chebyshev", steps, lo[, hi]) (polynomial preconditioner with the solver's shifts; hi defaults to the Gershgorin
     bound) | ("chebyshev", steps, lo, hi, shift) (fixed shift).  Result.precond_stats then holds its counters.
+    members: {"name": value} set through primme_set_member after the method preset and before `tweak`, e.g.
+    {"correctionParams.maxInnerIterations": 0, "projectionParams.projection": "primme_proj_refined"}; a string for an
+    enum member is an enumerator name (primme_constant_info); an unknown member or enumerator is a ValueError.
     """
     s = Session(op, comm=comm, dtype=dtype, backend=backend, complex_form=complex_form, mass=mass)
     try:

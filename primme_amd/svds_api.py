@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _ffi as F
 from .api import _resolve_backend
+from .members import apply_svds_members
 
 
 class SvdsResult:
@@ -123,8 +124,10 @@ def _precond_stats(lib):
 def svds(m, n, csr, numSvals=1, target="largest", method="normalequations", methodStage1="DEFAULT_METHOD",
          eps=1e-8, aNorm=0.0, backend="hip", dtype=np.float64, maxBlockSize=0, maxBasisSize=0, locking=None,
          maxMatvecs=0, v0=None, iseed=None, printLevel=0, return_vectors=True, targetShifts=None, precond=None,
-         user_precond=None):
-    """precond: None | "jacobi" | ("jacobi", shift) | ("chebyshev", steps, slo, shi[, sshift]) in singular value units
+         user_precond=None, members=None, tweak=None):
+    """members: {"name": value} set through primme_svds_set_member after primme_svds_set_method ("primme.<name>" and
+    "primmeStage2.<name>": through primme_set_member on that eigensolver block), then tweak(ps) has the last word.
+    precond: None | "jacobi" | ("jacobi", shift) | ("chebyshev", steps, slo, shi[, sshift]) in singular value units
     (include/primme_amd_svds.h): slo None = 0, shi None = the norm bound sqrt(|A|_1 |A|_inf), sshift omitted = 0 for
     target="smallest" and the norm bound for "largest"; SvdsResult.precond_stats then holds its counters.
     user_precond: an application preconditioner, a _ffi.SVDS_BLOCK_OP callback (same pointer conventions as the matvec)."""
@@ -197,6 +200,8 @@ def svds(m, n, csr, numSvals=1, target="largest", method="normalequations", meth
         mset = getattr(F, "PRIMME_" + methodStage1) if isinstance(methodStage1, str) and hasattr(F, "PRIMME_" + methodStage1) \
             else F.METHODS.get(methodStage1, 0) if isinstance(methodStage1, str) else methodStage1
         lib.primme_svds_set_method(F.SVDS_METHODS[method], mset, 0, C.byref(ps))
+        if members: apply_svds_members(lib, ps, members, keep)
+        if tweak is not None: tweak(ps)
 
         svals = np.zeros(numSvals, dtype=rdtype)
         rnorms = np.zeros(numSvals, dtype=rdtype)
@@ -264,7 +269,7 @@ class SvdsSession:
             raise RuntimeError(f"svds operator creation failed: {rc}")
 
     def solve(self, numSvals=1, target="largest", method="normalequations", methodStage1="DEFAULT_METHOD", eps=1e-8, aNorm=0.0,
-              maxBlockSize=0, maxBasisSize=0, maxMatvecs=0, iseed=None, precond=None):
+              maxBlockSize=0, maxBasisSize=0, maxMatvecs=0, iseed=None, precond=None, members=None, tweak=None):
         pc = parse_precond(precond, target)
         import torch
         lib, m, n = self.lib, self.m, self.n
@@ -285,6 +290,9 @@ class SvdsSession:
             _install_precond(lib, ps, self.op, pc, self.csr, False)
         mset = getattr(F, "PRIMME_" + methodStage1) if hasattr(F, "PRIMME_" + methodStage1) else F.METHODS.get(methodStage1, 0)
         lib.primme_svds_set_method(F.SVDS_METHODS[method], mset, 0, C.byref(ps))
+        keep = []
+        if members: apply_svds_members(lib, ps, members, keep)
+        if tweak is not None: tweak(ps)
         rdtype = self.dtype
         svals = np.zeros(numSvals, dtype=rdtype); rnorms = np.zeros(numSvals, dtype=rdtype)
         tdt = torch.float64 if rdtype == np.float64 else torch.float32
