@@ -11,6 +11,13 @@
  *   primme_amd_csr_complex_to_real       2n x 2n real-equivalent form of a complex matrix in the
  *                        interleaved (re, im) ordering: the operator hip_zprimme / hip_cprimme
  *                        are given for a Hermitian CSR matrix (primme_amd.h)
+ *   primme_amd_csr_row_patterns_diag     the scan of the diagonal-split row-pattern form of the device operator
+ *                        (primme_amd_kernels.h: HIPK_CSR_DIAG_PATTERNS): rows [row0, row0 + m) as one byte per row
+ *                        (pid[m + 1]) + a table of npat <= 256 patterns of stride ml (3/5/7/8): len[npat],
+ *                        off[npat * ml] = column - row, val[npat * ml] (0 at the diagonal's place) and dslot[npat], the
+ *                        index of the entry with offset 0 or -1.  values: double, or float when is_float.  Returns 1
+ *                        (nothing allocated) when the matrix does not qualify: a row longer than 8, a 257th pattern,
+ *                        two diagonal entries in a row, offsets out of reach
  *
  * 0-based int32 indices; values double (complex: re, im interleaved).  Returned arrays are
  * malloc'ed by the library: release them with primme_amd_host_free.  Return 0 on success,
@@ -31,6 +38,9 @@ int primme_amd_csr_tile_block_diagonal(int64_t n0, const int32_t *rowptr, const 
       int32_t **rowptr_out, int32_t **colind_out, double **values_out);
 int primme_amd_csr_complex_to_real(int64_t n, const int32_t *rowptr, const int32_t *colind,
       const double *values_re_im, int32_t **rowptr_out, int32_t **colind_out, double **values_out);
+int primme_amd_csr_row_patterns_diag(int64_t m, int64_t row0, const int32_t *rowptr, const int32_t *colind,
+      const void *values, int is_float, uint8_t **pid, int *npat, int *ml, int32_t **len, int32_t **off,
+      double **val, int32_t **dslot);
 void primme_amd_host_free(void *p);
 #ifdef __cplusplus
 }

@@ -344,6 +344,14 @@ typedef struct hipk_csr hipk_csr;
 int hipk_csr_create(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local, int64_t ncols_global,
       int64_t row0, const int32_t *rowptr_host, const int32_t *colind_host,
       const void *values_host, hipk_csr **A);
+/* The same with options.  HIPK_CSR_DIAG_PATTERNS: when the rows do not repeat exactly (see hipk_csr_format below), try the
+ * DIAGONAL-SPLIT row patterns — a row's pattern is its length, offsets, off-diagonal values and the position of its diagonal
+ * entry; the diagonal's value is streamed per row from hipk_csr_diag: stencil / lattice operator + potential, on-site
+ * disorder, graded shifts.  hipk_csr_create takes its flags from HIPK_SPMV_PAT_DIAG=1 in the environment (default: none). */
+#define HIPK_CSR_DIAG_PATTERNS 1u
+int hipk_csr_create_opts(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local, int64_t ncols_global,
+      int64_t row0, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, unsigned flags, hipk_csr **A);
 int hipk_csr_destroy(hipk_csr *A);
 /* launches on `hip_stream` (a hipStream_t passed by value as void*), or on the stream of
  * the creating context when NULL */
@@ -453,6 +461,9 @@ double hipk_csr_streamed_bytes(const hipk_csr *A);
 int hipk_set_spmv_format(int use_patterns);
 int hipk_csr_format(const hipk_csr *A);
 int hipk_csr_npatterns(const hipk_csr *A);
+/* 1 when the form in use is the diagonal-split flavour of the row patterns (HIPK_CSR_DIAG_PATTERNS; hipk_csr_format is 2 for
+ * both flavours): the product then streams the diagonal as well, nrows (1 + 3 s) bytes, nrows (1 + 4 s) fused */
+int hipk_csr_pattern_diag(const hipk_csr *A);
 double hipk_csr_product_bytes(const hipk_csr *A, int fused);
 /* Second stage of the reductions of the block-size-1 iteration: bit 1 fused residual pass, 2 Gram-Schmidt update, 4 fused
  * SpMV run it inside the producing launch (two-level, write-through partial sums, csrc/hipk_internal.h); 0 = a separate

@@ -262,6 +262,7 @@ def declare_kernels(lib):
         "hipk_csr_create_rect": [_vp, _i, _i64, _i64, _vp, _vp, _vp, P(_vp)],
         "primme_amd_mm_read": [C.c_char_p, P(_i64), P(_i64), P(_i64), P(_vp), P(_vp), P(_vp), P(_i)],
         "primme_amd_csr_transpose": [_i64, _i64, _vp, _vp, _vp, C.c_size_t, P(_vp), P(_vp), P(_vp)],
+        "primme_amd_csr_row_patterns_diag": [_i64, _i64, _vp, _vp, _vp, _i, P(_vp), P(_i), P(_i), P(_vp), P(_vp), P(_vp), P(_vp)],
         "primme_amd_csr_tile_block_diagonal": [_i64, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, P(_vp), P(_vp), P(_vp)],
         "primme_amd_operator_apply": [_vp, _vp, _vp, _i64, _vp, _i64, _i],
         "primme_amd_csr_complex_to_real": [_i64, _vp, _vp, _vp, P(_vp), P(_vp), P(_vp)],
@@ -317,6 +318,22 @@ def declare_chebyshev(lib):
     lib.hipk_csr_abs_rowsum_max.restype = C.c_int
 
 
+def declare_formats(lib):
+    """Creation with options and the queries of the one-column product's form: product library only (the CPU checker has one form)."""
+    P = C.POINTER
+    lib.hipk_csr_create_opts.argtypes = [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, C.c_uint, P(_vp)]
+    lib.hipk_csr_create_opts.restype = C.c_int
+    for name in ("hipk_csr_format", "hipk_csr_npatterns", "hipk_csr_pattern_diag"):
+        getattr(lib, name).argtypes = [_vp]
+        getattr(lib, name).restype = C.c_int
+    lib.hipk_set_spmv_format.argtypes = [_i]
+    lib.hipk_set_spmv_format.restype = C.c_int
+    lib.hipk_csr_product_bytes.argtypes = [_vp, _i]
+    lib.hipk_csr_product_bytes.restype = C.c_double
+
+
+HIPK_CSR_DIAG_PATTERNS = 1
+
 _cache = {}
 
 
@@ -337,5 +354,6 @@ def load_product():
         declare_solver(lib, "hip_")
         declare_kernels(lib)
         declare_chebyshev(lib)
+        declare_formats(lib)
         _cache["product"] = lib
     return _cache["product"]

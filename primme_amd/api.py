@@ -17,10 +17,15 @@ from .members import apply_members
 
 class Operator:
     """A sparse operator: CSR arrays (global column indices) or a Laplacian stencil,
-    rows [row0, row0+nrows) of an n x n matrix."""
+    rows [row0, row0+nrows) of an n x n matrix.
 
-    def __init__(self, n, csr=None, stencil=None, row0=0, nrows=None):
+    diag_patterns=True (real CSR matrices): when the rows repeat but for their diagonal entry (stencil or lattice operator +
+    potential / on-site term), the device keeps one byte per row and streams the diagonal (HIPK_CSR_DIAG_PATTERNS of
+    hipk_csr_create_opts) instead of the CSR arrays for the one-column products; same results, fewer bytes."""
+
+    def __init__(self, n, csr=None, stencil=None, row0=0, nrows=None, diag_patterns=False):
         self.n = int(n)
+        self.diag_patterns = bool(diag_patterns)
         self.csr = csr            # (rowptr int32, colind int32, values)
         self.stencil = stencil    # (nx, ny, nz)
         self.row0 = int(row0)
@@ -137,8 +142,14 @@ class Session:
                 for h in (rp2, ci2, va2): lib.primme_amd_host_free(h)
             else:
                 va = np.ascontiguousarray(va, dtype=self.dtype)
-                rc = lib.hipk_csr_create(ctx, self.dt, op.nrows, op.n, op.row0, rp.ctypes.data_as(C.c_void_p),
-                                         ci.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p), C.byref(A))
+                if getattr(op, "diag_patterns", False) and self.be.device:
+                    # the form of the device operator only: a checker that runs the host solver over host vectors has one form
+                    rc = lib.hipk_csr_create_opts(ctx, self.dt, op.nrows, op.n, op.row0, rp.ctypes.data_as(C.c_void_p),
+                                                  ci.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p),
+                                                  F.HIPK_CSR_DIAG_PATTERNS, C.byref(A))
+                else:
+                    rc = lib.hipk_csr_create(ctx, self.dt, op.nrows, op.n, op.row0, rp.ctypes.data_as(C.c_void_p),
+                                             ci.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p), C.byref(A))
         else:
             nx, ny, nz = (list(op.stencil) + [1, 1])[:3]
             rc = lib.hipk_stencil_create(ctx, self.dt, nx, ny or 1, nz or 1, op.row0, op.nrows, C.byref(A))

@@ -164,3 +164,93 @@ int primme_amd_csr_complex_to_real(int64_t n, const int32_t *rp, const int32_t *
    *rp_out = rp2; *ci_out = ci2; *val_out = va2;
    return 0;
 }
+
+/* Diagonal-split row patterns (device/hipk_sparse_pat.hip): a row's pattern is its length, its (column - row) offsets, its
+ * OFF-DIAGONAL values and the position of the entry with offset 0 (dslot, -1: the row stores no diagonal); the diagonal's
+ * value is not part of the pattern (the table holds 0 there) — the kernel reads it per row.  "-Laplacian + potential" has the
+ * patterns of the Laplacian.  Values enter the table as (double)(T) of the stored value, T = float when is_float.
+ * Returns 0 and pid[m + 1] (pid[m] = 0), npat, the table stride ml (3/5/7/8) and, per pattern, len[npat], off[npat * ml],
+ * val[npat * ml], dslot[npat] (all malloc'ed: primme_amd_host_free);  1 when the matrix does not qualify: a row longer than
+ * 8 entries, a 257th pattern, two entries of a row at offset 0 (one diagonal value per row is kept), an offset outside
+ * int32, or offsets so far apart that a byte offset within a 512-row chunk passes 2^31;  -5 out of memory. */
+#define RPD_MAXLEN 8
+#define RPD_MAXPAT 256
+#define RPD_SLOTS 1024                   /* open addressing, a power of two > 2 * RPD_MAXPAT */
+#define RPD_CHUNK_ROWS 2048              /* what the kernel's 32-bit lane offsets are checked for: 256 lanes x 8 rows */
+typedef struct { int32_t len, dslot; int32_t off[RPD_MAXLEN]; double val[RPD_MAXLEN]; } rpd_t;
+
+static uint32_t rpd_hash(const rpd_t *p) {
+   const unsigned char *b = (const unsigned char *)p;
+   uint32_t h = 2166136261u;               /* FNV-1a over the (zero-padded) record */
+   for (size_t i = 0; i < sizeof(rpd_t); i++) { h ^= b[i]; h *= 16777619u; }
+   return h;
+}
+
+int primme_amd_csr_row_patterns_diag(int64_t m, int64_t row0, const int32_t *rp, const int32_t *ci, const void *values,
+      int is_float, uint8_t **pid_out, int *npat_out, int *ml_out, int32_t **len_out, int32_t **off_out, double **val_out,
+      int32_t **dslot_out) {
+   *pid_out = NULL; *len_out = NULL; *off_out = NULL; *val_out = NULL; *dslot_out = NULL; *npat_out = 0; *ml_out = 0;
+   if (m <= 0) return 1;
+   rpd_t *pats = (rpd_t *)malloc(sizeof(rpd_t) * RPD_MAXPAT);
+   int16_t *slot = (int16_t *)malloc(sizeof(int16_t) * RPD_SLOTS);
+   uint8_t *pid = (uint8_t *)calloc((size_t)m + 1, 1);
+   if (!pats || !slot || !pid) { free(pats); free(slot); free(pid); return -5; }
+   for (int i = 0; i < RPD_SLOTS; i++) slot[i] = -1;
+   int npat = 0, maxlen = 0, prev = -1, rc = 0;
+   rpd_t cur;
+   for (int64_t i = 0; i < m && !rc; i++) {
+      const int len = rp[i + 1] - rp[i];
+      if (len > RPD_MAXLEN || len < 0) { rc = 1; break; }
+      memset(&cur, 0, sizeof cur);
+      cur.len = len; cur.dslot = -1;
+      for (int e = 0; e < len; e++) {
+         const int64_t off = (int64_t)ci[rp[i] + e] - (row0 + i);
+         if (off > INT32_MAX || off < INT32_MIN) { rc = 1; break; }
+         cur.off[e] = (int32_t)off;
+         if (off == 0) {
+            if (cur.dslot >= 0) { rc = 1; break; }       /* a second diagonal entry */
+            cur.dslot = e;                                 /* its value stays 0 in the key */
+         } else cur.val[e] = is_float ? (double)((const float *)values)[rp[i] + e] : ((const double *)values)[rp[i] + e];
+      }
+      if (rc) break;
+      int id = -1;
+      if (prev >= 0 && !memcmp(&pats[prev], &cur, sizeof cur)) id = prev;     /* the common case: same as the row above */
+      else {
+         uint32_t h = rpd_hash(&cur) & (RPD_SLOTS - 1);
+         while (slot[h] >= 0 && memcmp(&pats[slot[h]], &cur, sizeof cur)) h = (h + 1) & (RPD_SLOTS - 1);
+         if (slot[h] >= 0) id = slot[h];
+         else {
+            if (npat >= RPD_MAXPAT) { rc = 1; break; }
+            id = npat;
+            pats[npat++] = cur;
+            slot[h] = (int16_t)id;
+         }
+      }
+      pid[i] = (uint8_t)id;
+      prev = id;
+      if (len > maxlen) maxlen = len;
+   }
+   if (!rc) {
+      int64_t minoff = 0, maxoff = 0;
+      for (int p = 0; p < npat; p++)
+         for (int e = 0; e < pats[p].len; e++) {
+            if (pats[p].off[e] < minoff) minoff = pats[p].off[e];
+            if (pats[p].off[e] > maxoff) maxoff = pats[p].off[e];
+         }
+      if ((maxoff - minoff + RPD_CHUNK_ROWS) * (int64_t)(is_float ? 4 : 8) >= ((int64_t)1 << 31)) rc = 1;
+   }
+   free(slot);
+   if (rc) { free(pats); free(pid); return rc; }
+   const int ml = maxlen <= 3 ? 3 : maxlen <= 5 ? 5 : maxlen <= 7 ? 7 : 8;
+   int32_t *tlen = (int32_t *)calloc((size_t)npat, sizeof(int32_t)), *tds = (int32_t *)calloc((size_t)npat, sizeof(int32_t));
+   int32_t *toff = (int32_t *)calloc((size_t)npat * ml, sizeof(int32_t));
+   double *tval = (double *)calloc((size_t)npat * ml, sizeof(double));
+   if (!tlen || !tds || !toff || !tval) { free(pats); free(pid); free(tlen); free(tds); free(toff); free(tval); return -5; }
+   for (int p = 0; p < npat; p++) {
+      tlen[p] = pats[p].len; tds[p] = pats[p].dslot;
+      for (int e = 0; e < pats[p].len; e++) { toff[(size_t)p * ml + e] = pats[p].off[e]; tval[(size_t)p * ml + e] = pats[p].val[e]; }
+   }
+   free(pats);
+   *pid_out = pid; *npat_out = npat; *ml_out = ml; *len_out = tlen; *off_out = toff; *val_out = tval; *dslot_out = tds;
+   return 0;
+}

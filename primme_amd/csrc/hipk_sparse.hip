@@ -51,10 +51,14 @@ struct hipk_csr {
 struct hipk_pb;
 struct hipk_pat;
 extern "C" int hipk_pat_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t row0, const int32_t *rp, const int32_t *ci, const void *val, hipk_pat **out);
+extern "C" int hipk_pat_build_diag(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t row0, const int32_t *rp, const int32_t *ci, const void *val,
+      const void *diag_dev, hipk_pat **out);
+extern "C" int hipk_pat_diag(const hipk_pat *B);
 extern "C" int hipk_pat_matvec(const hipk_pat *B, void *hip_stream, int gx, const void *x, void *y, int64_t halo_lo, int64_t halo_hi, const void *xlo,
       const void *xhi, const double *norm2, int np2, void *xout, double *partials, const hipk_fin_args *fa);
 extern "C" void hipk_pat_destroy(hipk_pat *B);
 extern "C" int hipk_pat_grid(const hipk_pat *B, int num_cu);
+extern "C" int hipk_pat_grid_kind(const hipk_pat *B, int num_cu, int kind);      /* 0 product, 1 fused tail, 2 Chebyshev step */
 extern "C" double hipk_pat_bytes(const hipk_pat *B, int fused);
 extern "C" int hipk_pat_npatterns(const hipk_pat *B);
 extern "C" int hipk_pat_enabled(void);
@@ -575,7 +579,7 @@ jacobi_kernel(const T *__restrict__ diag, JacShift sh, double min_den, const T *
 
 static int csr_create_impl(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local,
       int64_t ncols_global, int64_t row0, int64_t x0, int64_t xlen, const int32_t *rowptr_host,
-      const int32_t *colind_host, const void *values_host, hipk_csr **out) {
+      const int32_t *colind_host, const void *values_host, unsigned flags, hipk_csr **out) {
    if (dt != HIPK_F64 && dt != HIPK_F32 && dt != HIPK_C64 && dt != HIPK_C32) return -44;
    if (nrows_local >= ((int64_t)1 << 31)) return -1;
    hipk_csr *A = (hipk_csr *)calloc(1, sizeof(hipk_csr));
@@ -706,20 +710,34 @@ static int csr_create_impl(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local,
    if (x0 == row0 && xlen == nrows_local && (dt == HIPK_F64 || dt == HIPK_F32) && !A->pb) {
       const int rcp = hipk_pat_build(ctx, dt, nrows_local, row0, rowptr_host, colind_host, values_host, &A->pat);
       if (rcp < 0) return rcp;
+      /* HIPK_CSR_DIAG_PATTERNS: the exact scan gave up — rows that repeat but for their diagonal entry (stencil / lattice
+       * operator + potential) take the diagonal-split flavour, which streams A->diag beside the pattern bytes */
+      if (!A->pat && (flags & HIPK_CSR_DIAG_PATTERNS)) {
+         const int rcd = hipk_pat_build_diag(ctx, dt, nrows_local, row0, rowptr_host, colind_host, values_host, A->diag, &A->pat);
+         if (rcd < 0) return rcd;
+      }
    }
    *out = A;
    return 0;
 }
 
+extern "C" int hipk_csr_create_opts(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local,
+      int64_t ncols_global, int64_t row0, const int32_t *rowptr_host,
+      const int32_t *colind_host, const void *values_host, unsigned flags, hipk_csr **out) {
+   return csr_create_impl(ctx, dt, nrows_local, ncols_global, row0, row0, nrows_local, rowptr_host,
+         colind_host, values_host, flags, out);
+}
+/* the flags of hipk_csr_create: HIPK_SPMV_PAT_DIAG=1 in the environment asks for the diagonal-split row patterns (default: none) */
 extern "C" int hipk_csr_create(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local,
       int64_t ncols_global, int64_t row0, const int32_t *rowptr_host,
       const int32_t *colind_host, const void *values_host, hipk_csr **out) {
-   return csr_create_impl(ctx, dt, nrows_local, ncols_global, row0, row0, nrows_local, rowptr_host,
-         colind_host, values_host, out);
+   const char *e = getenv("HIPK_SPMV_PAT_DIAG");
+   return hipk_csr_create_opts(ctx, dt, nrows_local, ncols_global, row0, rowptr_host, colind_host, values_host,
+         (e && atoi(e) != 0) ? HIPK_CSR_DIAG_PATTERNS : 0u, out);
 }
 extern "C" int hipk_csr_create_rect(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows, int64_t ncols,
       const int32_t *rowptr_host, const int32_t *colind_host, const void *values_host, hipk_csr **out) {
-   return csr_create_impl(ctx, dt, nrows, ncols, 0, 0, ncols, rowptr_host, colind_host, values_host, out);
+   return csr_create_impl(ctx, dt, nrows, ncols, 0, 0, ncols, rowptr_host, colind_host, values_host, 0u, out);
 }
 
 extern "C" int hipk_stencil_create(hipk_ctx *ctx, hipk_dtype dt, int nx, int ny, int nz,
@@ -802,6 +820,8 @@ extern "C" int hipk_csr_format(const hipk_csr *A) {
    return A->pb ? 1 : 0;
 }
 extern "C" int hipk_csr_npatterns(const hipk_csr *A) { return A && A->pat ? hipk_pat_npatterns(A->pat) : 0; }
+/* 1 when the form in use is the row-pattern form in its diagonal-split flavour (the product streams the diagonal) */
+extern "C" int hipk_csr_pattern_diag(const hipk_csr *A) { return hipk_csr_format(A) == 2 && hipk_pat_diag(A->pat); }
 /* bytes ONE one-column product (fused = with the second output of hipk_csr_matvec_scaled) moves through HBM in the form in use */
 extern "C" double hipk_csr_product_bytes(const hipk_csr *A, int fused) {
    if (!A) return 0.0;
@@ -977,7 +997,7 @@ extern "C" int hipk_csr_cheb_step(hipk_csr *A, void *hip_stream, int nx, const h
    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : A->ctx->stream;
    const size_t es = A->dt == HIPK_F64 ? 8 : 4;
    if (A->pat && hipk_pat_enabled()) {
-      const int gx = hipk_pat_grid(A->pat, A->ctx->num_cu);
+      const int gx = hipk_pat_grid_kind(A->pat, A->ctx->num_cu, 2);
       for (int c = 0; c < nx; c++) {
          const double cf[4] = {coef->cy[c], coef->cp[c], coef->cx[c], coef->cw[c]};
          const int pslot = hipk_prof_begin_s(HIPK_PROF_SPMV, st, hipk_pat_bytes(A->pat, 0) + (Yprev ? 2.0 : 1.0) * A->nrows * es,
@@ -1062,7 +1082,7 @@ extern "C" int hipk_csr_matvec_scaled(hipk_csr *A, hipk_ctx *ctx, const void *x,
       return 0;
    }
    const bool pat = A->pat && hipk_pat_enabled();
-   const int gx = pat ? hipk_pat_grid(A->pat, ctx->num_cu) : ((A->ntiles + 7) / 8) * 8;
+   const int gx = pat ? hipk_pat_grid_kind(A->pat, ctx->num_cu, 1) : ((A->ntiles + 7) / 8) * 8;
    if (hipk_reserve_partials(ctx, (size_t)gx)) return -2;
    const double es = A->dt == HIPK_F64 ? 8 : 4;
    /* the tail of a block-size-1 iteration without second-stage launches (hipk_tail_defer): |t|^2 may still be np2 partial sums

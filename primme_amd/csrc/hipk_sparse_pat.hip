@@ -21,8 +21,19 @@
  * summation order of the per-row terms).  Built by hipk_csr_create when the whole matrix has at most 256 patterns of at
  * most 8 entries (the scan gives up at the 257th pattern: a matrix that does not qualify costs a few hundred rows);
  * the CSR arrays stay for the block kernels.  HIPK_SPMV_PAT=0 / hipk_set_spmv_format(0) switch it off (A/B, tests).
+ *
+ * The DIAGONAL-SPLIT flavour (opt-in: HIPK_CSR_DIAG_PATTERNS of hipk_csr_create_opts, tried only after the exact scan has given
+ * up): a varying diagonal — a potential, an on-site energy, a graded shift on a stencil or lattice operator — makes every row
+ * its own pattern.  There a row's pattern is its length, its offsets, its OFF-DIAGONAL values and the position of the entry
+ * with offset 0 (dslot, -1: none; kept in LDS beside the lengths); the diagonal's value is not in the table (0 stands there)
+ * but streamed per row from the matrix's diagonal array (hipk_csr_diag, typed T): m*s more bytes per product, m*(1 + 3s) /
+ * m*(1 + 4s) fused.  A lane's pair of diagonal values is one 16-byte access in the batch of the gathers; entry e of a row
+ * multiplies e == dslot ? d : table value, so the products, their order and y are still those of csr_stream_kernel, bit for
+ * bit ((double)(T) of the stored value, as the table converts).  The scan is plain C (csr_tools.c:
+ * primme_amd_csr_row_patterns_diag).  Every kernel below has a DIAG template parameter; DIAG = false compiles to what it was.
  */
 #include "hipk_internal.h"
+#include "primme_amd_io.h"
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -38,6 +49,14 @@
 #ifndef HIPK_PAT_WPS
 #define HIPK_PAT_WPS 6
 #endif
+/* the same for the diagonal-split instantiations (two more values per pair in flight, a select per entry): the most
+ * workgroups per CU at which the instantiation keeps everything in registers (-Rpass-analysis=kernel-resource-usage: at 6 the
+ * widths 7 and 8 and the Chebyshev step of width 5 use scratch, at 5 width 8 and the Chebyshev step of width 7 still do;
+ * profiles/pat_diag_spmv.md has the table).  kind: 0 product, 1 fused tail, 2 Chebyshev step */
+static constexpr int pat_wps_diag(int ml, int kind) {
+   const int w = ml <= 3 ? 6 : ml <= 5 ? (kind == 2 ? 5 : 6) : ml <= 7 ? (kind == 2 ? 4 : 5) : 4;
+   return w < HIPK_PAT_WPS ? w : HIPK_PAT_WPS;
+}
 
 struct hipk_pat {
    hipk_ctx *ctx;
@@ -49,6 +68,8 @@ struct hipk_pat {
    double *tval;                   /* device [npat * ml] */
    int32_t *tlen;                  /* device [npat] */
    int32_t minoff, maxoff;         /* smallest (<= 0) and largest (>= 0) column - row over all patterns */
+   int32_t *tds;                   /* diagonal-split form: device [npat] position of the offset-0 entry (-1: none), else NULL */
+   const void *diag;               /* diagonal-split form: the matrix's diagonal (device [nrows] of dt, owned by the hipk_csr) */
 };
 
 /* s + v*x with the product and the sum rounded SEPARATELY (what the tile kernel does through its LDS staging): the default
@@ -57,6 +78,12 @@ __device__ __forceinline__ double pat_mul_add(double s, double v, double x) {
 #pragma clang fp contract(off)
    const double p = v * x;
    return s + p;
+}
+
+/* the value entry i of the table multiplies with; DIAG: the row's diagonal d where the entry e is the row's diagonal slot ds */
+template <bool DIAG> __device__ __forceinline__ double pat_tval(const double *s_val, int i, int e, int ds, const double &d) {
+   if constexpr (DIAG) return e == ds ? d : s_val[i];
+   else return s_val[i];
 }
 
 /* the outputs: plain stores by default; HIPK_PAT_NT_STORES=1 (build-time, A/B builds) marks them non-temporal */
@@ -73,17 +100,24 @@ template <typename T> __device__ __forceinline__ void pat_store(T *p, T v) {
  * the row's own x (table: offset 0, value 0) and is not added */
 /* CHEB (hipk_cheb.hip: one step of the Chebyshev recurrence with the product inside): the row sum s is not stored as it is but as
  * cy x(r) + cp yp(r) + cx xr(r) + cw s, x being the iterate the product gathers from; y may be yp (row-local), never x */
+/* DIAG (diagonal-split form): the same block also carries the diagonal array and the table of diagonal positions */
 template <typename T> struct pat_cheb { double cy, cp, cx, cw; const T *xr, *yp; };
 struct pat_nocheb {};
-template <typename T, bool CHEB> struct pat_ep { typedef pat_nocheb type; };
-template <typename T> struct pat_ep<T, true> { typedef pat_cheb<T> type; };
+template <typename T> struct pat_cheb_dg { double cy, cp, cx, cw; const T *xr, *yp; const T *diag; const int32_t *tds; };
+template <typename T> struct pat_dg { const T *diag; const int32_t *tds; };
+template <typename T, bool CHEB, bool DIAG = false> struct pat_ep { typedef pat_nocheb type; };
+template <typename T> struct pat_ep<T, true, false> { typedef pat_cheb<T> type; };
+template <typename T> struct pat_ep<T, false, true> { typedef pat_dg<T> type; };
+template <typename T> struct pat_ep<T, true, true> { typedef pat_cheb_dg<T> type; };
 
-template <typename T, int ML, int RPL, bool FUSED, bool HALO, bool GUARD, bool CHEB = false>
+template <typename T, int ML, int RPL, bool FUSED, bool HALO, bool GUARD, bool CHEB = false, bool DIAG = false>
 __device__ __forceinline__ void pat_trip(const int (&p)[RPL], const int64_t (&r)[RPL], const double *s_val, const int32_t *s_off,
       const int32_t *s_len, int64_t nrows, const T *__restrict__ x, T *__restrict__ y, int64_t halo_lo, const T *__restrict__ xlo,
-      const T *__restrict__ xhi, double a, T *__restrict__ xout, double &dotp, const typename pat_ep<T, CHEB>::type &ch) {
+      const T *__restrict__ xhi, double a, T *__restrict__ xout, double &dotp, const typename pat_ep<T, CHEB, DIAG>::type &ch,
+      const int32_t *s_ds = nullptr) {
    const int64_t last = nrows - 1;
    double xg[RPL][ML], xo[RPL];
+   double dg[RPL];                                   /* DIAG: the rows' diagonal values (of the clamped row) */
 #pragma unroll
    for (int u = 0; u < RPL; u++) {
       const int64_t rc = (GUARD && r[u] > last) ? last : r[u];
@@ -100,15 +134,18 @@ __device__ __forceinline__ void pat_trip(const int (&p)[RPL], const int64_t (&r)
          }
       }
       if (FUSED || CHEB) xo[u] = (double)x[rc];
+      if constexpr (DIAG) dg[u] = (double)ch.diag[rc];
    }
 #pragma unroll
    for (int u = 0; u < RPL; u++) {
       const int len = s_len[p[u]];
+      int ds = -1;
+      if constexpr (DIAG) ds = s_ds[p[u]];
       double s = 0.0;
 #pragma unroll
       for (int e = 0; e < ML; e++) {
          const double xv = FUSED ? (double)(T)(a * xg[u][e]) : xg[u][e];
-         const double t = pat_mul_add(s, s_val[p[u] * ML + e], xv);
+         const double t = pat_mul_add(s, pat_tval<DIAG>(s_val, p[u] * ML + e, e, ds, dg[u]), xv);
          s = e < len ? t : s;
       }
       if (!GUARD || r[u] < nrows) {
@@ -169,14 +206,17 @@ template <typename T> __device__ __forceinline__ void pat_bstore2(__amdgpu_buffe
  *   unsigned, and the range check is exact);  ry / ro: y, xout from the chunk's first row;  rowb[u]: byte offset of the lane's
  *   u-th pair within the chunk */
 /* CHEB: ro is the descriptor of the right-hand side xr, rq the one of yp (both from the chunk's first row, as ry) */
-template <typename T, int ML, int RPL, bool FUSED, bool CHEB = false>
+/* DIAG: rd is the descriptor of the diagonal from the chunk's first row (as ry): the pair's two values are one access */
+template <typename T, int ML, int RPL, bool FUSED, bool CHEB = false, bool DIAG = false>
 __device__ __forceinline__ void pat_trip_inner(const int (&p)[2 * RPL], const double *s_val, const int32_t *s_off, const int32_t *s_len,
       __amdgpu_buffer_rsrc_t rx, __amdgpu_buffer_rsrc_t ry, __amdgpu_buffer_rsrc_t ro, int32_t minoff, bool near,
-      const uint32_t (&rowb)[RPL], double a, double &dotp, const typename pat_ep<T, CHEB>::type &ch, __amdgpu_buffer_rsrc_t rq) {
+      const uint32_t (&rowb)[RPL], double a, double &dotp, const typename pat_ep<T, CHEB, DIAG>::type &ch, __amdgpu_buffer_rsrc_t rq,
+      __amdgpu_buffer_rsrc_t rd, const int32_t *s_ds = nullptr) {
    constexpr int SH = sizeof(T) == 8 ? 3 : 2;
    const uint32_t ownb = (uint32_t)(-minoff) << SH;
    double xa[RPL][ML], xb[RPL][ML], oa[RPL], ob[RPL];
    double ra[RPL], rb[RPL], qa[RPL], qb[RPL];        /* CHEB: the pair's entries of xr and yp */
+   double da[RPL], db[RPL];                          /* DIAG: the pair's diagonal values */
 #pragma unroll
    for (int u = 0; u < RPL; u++) {
       const int pa = p[2 * u], pb = p[2 * u + 1];
@@ -185,6 +225,7 @@ __device__ __forceinline__ void pat_trip_inner(const int (&p)[2 * RPL], const do
          qa[u] = 0.0; qb[u] = 0.0;
          if (ch.yp) pat_bload2<T>(rq, rowb[u], 0, qa[u], qb[u]);
       }
+      if constexpr (DIAG) pat_bload2<T>(rd, rowb[u], 0, da[u], db[u]);
       /* both rows with the first row's offsets: one access per entry for the pair (an entry past the end of x reads as 0: the
        * descriptor's range check) ... */
 #pragma unroll
@@ -211,11 +252,14 @@ __device__ __forceinline__ void pat_trip_inner(const int (&p)[2 * RPL], const do
    for (int u = 0; u < RPL; u++) {
       const int pa = p[2 * u], pb = p[2 * u + 1];
       const int la = s_len[pa], lb = s_len[pb];
+      int dsa = -1, dsb = -1;
+      if constexpr (DIAG) { dsa = s_ds[pa]; dsb = s_ds[pb]; }
       double sa = 0.0, sb = 0.0;
 #pragma unroll
       for (int e = 0; e < ML; e++) {
          const double va = FUSED ? (double)(T)(a * xa[u][e]) : xa[u][e], vb = FUSED ? (double)(T)(a * xb[u][e]) : xb[u][e];
-         const double ta = pat_mul_add(sa, s_val[pa * ML + e], va), tb = pat_mul_add(sb, s_val[pb * ML + e], vb);
+         const double ta = pat_mul_add(sa, pat_tval<DIAG>(s_val, pa * ML + e, e, dsa, da[u]), va),
+                      tb = pat_mul_add(sb, pat_tval<DIAG>(s_val, pb * ML + e, e, dsb, db[u]), vb);
          sa = e < la ? ta : sa;
          sb = e < lb ? tb : sb;
       }
@@ -258,13 +302,13 @@ __device__ __forceinline__ void pat_ids(const uint8_t *__restrict__ pid, int64_t
  * contiguous window and the +-nx / +-plane neighbours of a stencil row are found in ITS L2.
  * RPL rows per lane and trip (256 apart: every access of a wave stays unit-stride): all their gathers are issued before
  * the first product — the bytes a wave keeps in flight are what bounds a kernel whose rows need 9 bytes from HBM. */
-template <typename T, int ML, int RPL, int WPS, bool FUSED, bool HALO, bool CHEB = false>
+template <typename T, int ML, int RPL, int WPS, bool FUSED, bool HALO, bool CHEB = false, bool DIAG = false>
 __global__ void __launch_bounds__(HIPK_BLOCK, WPS)
 pat_kernel(const uint8_t *__restrict__ pid, const int32_t *__restrict__ toff, const double *__restrict__ tval,
       const int32_t *__restrict__ tlen, int npat, int64_t nrows, const T *__restrict__ x, T *__restrict__ y,
       int64_t halo_lo, const T *__restrict__ xlo, const T *__restrict__ xhi, const double *__restrict__ norm2, int np2,
       T *__restrict__ xout, double *__restrict__ partials, hipk_fin_args fa, int32_t minoff, int32_t maxoff,
-      typename pat_ep<T, CHEB>::type ch) {
+      typename pat_ep<T, CHEB, DIAG>::type ch) {
    extern __shared__ double pat_sh[];
    __shared__ int s_last;
    __shared__ double s_n2[4];
@@ -273,6 +317,12 @@ pat_kernel(const uint8_t *__restrict__ pid, const int32_t *__restrict__ toff, co
    int32_t *s_len = s_off + (size_t)npat * ML;                 /* [npat] */
    for (int i = threadIdx.x; i < npat * ML; i += HIPK_BLOCK) { s_val[i] = tval[i]; s_off[i] = toff[i]; }
    for (int i = threadIdx.x; i < npat; i += HIPK_BLOCK) s_len[i] = tlen[i];
+   const int32_t *s_ds = nullptr;                              /* DIAG: [npat] behind s_len */
+   if constexpr (DIAG) {
+      int32_t *w = s_len + npat;
+      for (int i = threadIdx.x; i < npat; i += HIPK_BLOCK) w[i] = ch.tds[i];
+      s_ds = w;
+   }
    /* np2 > 0: norm2 points at the np2 partial sums of |t|^2 the Gram-Schmidt update left (hipk_tail_defer): this workgroup
     * adds them itself, in the order every other workgroup and hipk_tail_finish use — no second-stage launch in between */
    if (FUSED && np2 > 0) hipk_block_sum256_put(norm2, np2, s_n2);
@@ -311,19 +361,21 @@ pat_kernel(const uint8_t *__restrict__ pid, const int32_t *__restrict__ toff, co
          const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(y + r0), 0, (int)(ybytes < 0x7fffffff ? ybytes : 0x7fffffff), 0x00020000);
          const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)((FUSED ? xout : y) + r0), 0, (int)(ybytes < 0x7fffffff ? ybytes : 0x7fffffff), 0x00020000);
          const bool near = r0 + CH + maxoff >= nrows;               /* some row of the chunk may reference the last column */
+         __amdgpu_buffer_rsrc_t rd = ry;
+         if constexpr (DIAG) rd = __builtin_amdgcn_make_buffer_rsrc((void *)(ch.diag + r0), 0, (int)(ybytes < 0x7fffffff ? ybytes : 0x7fffffff), 0x00020000);
          if constexpr (CHEB) {
             const int rbytes = (int)(ybytes < 0x7fffffff ? ybytes : 0x7fffffff);
             const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void *)(ch.xr + r0), 0, rbytes, 0x00020000);
             const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)((ch.yp ? ch.yp : ch.xr) + r0), 0, rbytes, 0x00020000);
-            pat_trip_inner<T, ML, RPL, FUSED, true>(p, s_val, s_off, s_len, rx, ry, rr, minoff, near, rowb, a, dotp, ch, rq);
+            pat_trip_inner<T, ML, RPL, FUSED, true, DIAG>(p, s_val, s_off, s_len, rx, ry, rr, minoff, near, rowb, a, dotp, ch, rq, rd, s_ds);
          } else {
-            pat_trip_inner<T, ML, RPL, FUSED, false>(p, s_val, s_off, s_len, rx, ry, ro, minoff, near, rowb, a, dotp, ch, ro);
+            pat_trip_inner<T, ML, RPL, FUSED, false, DIAG>(p, s_val, s_off, s_len, rx, ry, ro, minoff, near, rowb, a, dotp, ch, ro, rd, s_ds);
          }
       } else {
          int64_t r[NR];
 #pragma unroll
          for (int v = 0; v < NR; v++) r[v] = r0 + 2 * (threadIdx.x + (int64_t)(v >> 1) * HIPK_BLOCK) + (v & 1);
-         pat_trip<T, ML, NR, FUSED, HALO, true, CHEB>(p, r, s_val, s_off, s_len, nrows, x, y, halo_lo, xlo, xhi, a, xout, dotp, ch);
+         pat_trip<T, ML, NR, FUSED, HALO, true, CHEB, DIAG>(p, r, s_val, s_off, s_len, nrows, x, y, halo_lo, xlo, xhi, a, xout, dotp, ch, s_ds);
       }
    }
    if (FUSED) {
@@ -343,6 +395,7 @@ extern "C" void hipk_pat_destroy(hipk_pat *B) {
    if (B->toff) (void)hipFree(B->toff);
    if (B->tval) (void)hipFree(B->tval);
    if (B->tlen) (void)hipFree(B->tlen);
+   if (B->tds) (void)hipFree(B->tds);
    free(B);
 }
 
@@ -422,28 +475,79 @@ extern "C" int hipk_pat_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t r
    return 0;
 }
 
+/* the diagonal-split form (header comment): the scan is primme_amd_csr_row_patterns_diag; diag_dev is the matrix's diagonal in
+ * HBM ([m] of dt; stays the caller's, must outlive the form).  Same return values as hipk_pat_build */
+extern "C" int hipk_pat_build_diag(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t row0, const int32_t *rp, const int32_t *ci,
+      const void *val, const void *diag_dev, hipk_pat **out) {
+   *out = NULL;
+   if ((dt != HIPK_F64 && dt != HIPK_F32) || m <= 0 || !diag_dev) return 1;
+   uint8_t *pid = NULL;
+   int32_t *tlen = NULL, *toff = NULL, *tds = NULL;
+   double *tval = NULL;
+   int npat = 0, ml = 0;
+   const int rcs = primme_amd_csr_row_patterns_diag(m, row0, rp, ci, val, dt == HIPK_F32, &pid, &npat, &ml, &tlen, &toff, &tval, &tds);
+   if (rcs) return rcs > 0 ? 1 : -2;
+   int32_t minoff = 0, maxoff = 0;
+   for (int p = 0; p < npat; p++)
+      for (int e = 0; e < tlen[p]; e++) {
+         const int32_t o = toff[(size_t)p * ml + e];
+         if (o < minoff) minoff = o;
+         if (o > maxoff) maxoff = o;
+      }
+   int rc = 0;
+   hipk_pat *B = (hipk_pat *)calloc(1, sizeof(hipk_pat));
+   if (!B) rc = -2;
+   if (!rc) {
+      B->ctx = ctx; B->dt = dt; B->nrows = m; B->npat = npat; B->ml = ml; B->minoff = minoff; B->maxoff = maxoff; B->diag = diag_dev;
+      const size_t nt = (size_t)npat * ml;
+      if (hipk_malloc(ctx, (size_t)m + 1, (void **)&B->pid) || hipk_malloc(ctx, nt * 4, (void **)&B->toff) || hipk_malloc(ctx, nt * 8, (void **)&B->tval) ||
+            hipk_malloc(ctx, (size_t)npat * 4, (void **)&B->tlen) || hipk_malloc(ctx, (size_t)npat * 4, (void **)&B->tds)) rc = -2;
+      else if (hipk_upload(ctx, B->pid, pid, (size_t)m + 1) || hipk_upload(ctx, B->toff, toff, nt * 4) || hipk_upload(ctx, B->tval, tval, nt * 8) ||
+            hipk_upload(ctx, B->tlen, tlen, (size_t)npat * 4) || hipk_upload(ctx, B->tds, tds, (size_t)npat * 4)) rc = -1;
+   }
+   free(pid); free(tlen); free(toff); free(tval); free(tds);
+   if (rc) { hipk_pat_destroy(B); return rc; }
+   *out = B;
+   return 0;
+}
+
 extern "C" int hipk_pat_npatterns(const hipk_pat *B) { return B ? B->npat : 0; }
+extern "C" int hipk_pat_diag(const hipk_pat *B) { return B && B->tds ? 1 : 0; }
 /* workgroups of a launch (a multiple of 8: the XCD schedule); the fused form writes one partial sum per workgroup */
-extern "C" int hipk_pat_grid(const hipk_pat *B, int num_cu) {
+extern "C" int hipk_pat_grid_kind(const hipk_pat *B, int num_cu, int kind) {
    const int rpl = PAT_RPL_FOR(B->ml);
    const int64_t nch = (B->nrows + (int64_t)2 * HIPK_BLOCK * rpl - 1) / ((int64_t)2 * HIPK_BLOCK * rpl);   /* RPL pairs of rows per lane and trip */
-   int64_t g = (int64_t)num_cu * HIPK_PAT_WPS;        /* the resident set: HIPK_PAT_WPS workgroups per CU (__launch_bounds__) */
+   int64_t g = (int64_t)num_cu * (B->tds ? pat_wps_diag(B->ml, kind) : HIPK_PAT_WPS);      /* the resident set: the workgroups per CU the kernel of this kind (0 product, 1 fused tail, 2 Chebyshev step) is compiled for (__launch_bounds__) */
    if (g > nch) g = nch;
    g = g / 8 * 8;                                     /* a multiple of 8 that does not exceed it: the XCD schedule */
    return (int)(g < 8 ? 8 : g);
 }
-/* bytes one product moves through HBM: the pattern bytes, x once, y (and the second output of the fused form) */
+extern "C" int hipk_pat_grid(const hipk_pat *B, int num_cu) { return hipk_pat_grid_kind(B, num_cu, 0); }
+/* bytes one product moves through HBM: the pattern bytes, x once, y (and the second output of the fused form; and the
+ * diagonal of the diagonal-split form) */
 extern "C" double hipk_pat_bytes(const hipk_pat *B, int fused) {
    const double es = B->dt == HIPK_F64 ? 8 : 4;
-   return (double)B->nrows * (1.0 + (fused ? 3.0 : 2.0) * es);
+   return (double)B->nrows * (1.0 + ((fused ? 3.0 : 2.0) + (B->tds ? 1.0 : 0.0)) * es);
 }
 
 template <typename T, bool FUSED, bool HALO>
 static void pat_launch_ml(const hipk_pat *B, hipStream_t st, int gx, const T *x, T *y, int64_t halo_lo, const T *xlo, const T *xhi,
       const double *norm2, int np2, T *xout, double *partials, const hipk_fin_args &fa) {
-   const size_t shm = (size_t)B->npat * B->ml * 12 + (size_t)B->npat * 4 + 8;
+   const size_t shm = (size_t)B->npat * B->ml * 12 + (size_t)B->npat * (B->tds ? 8 : 4) + 8;
 #define PATL(MLV) hipLaunchKernelGGL((pat_kernel<T, MLV, PAT_RPL_FOR(MLV), HIPK_PAT_WPS, FUSED, HALO>), dim3(gx), dim3(HIPK_BLOCK), shm, st, B->pid, B->toff, B->tval, B->tlen, B->npat, \
          B->nrows, x, y, halo_lo, xlo, xhi, norm2, np2, xout, partials, fa, B->minoff, B->maxoff, pat_nocheb())
+#define PATLD(MLV) hipLaunchKernelGGL((pat_kernel<T, MLV, PAT_RPL_FOR(MLV), pat_wps_diag(MLV, FUSED ? 1 : 0), FUSED, HALO, false, true>), dim3(gx), dim3(HIPK_BLOCK), shm, st, B->pid, B->toff, B->tval, B->tlen, B->npat, \
+         B->nrows, x, y, halo_lo, xlo, xhi, norm2, np2, xout, partials, fa, B->minoff, B->maxoff, dg)
+   if (B->tds) {
+      const pat_dg<T> dg = {(const T *)B->diag, B->tds};
+      switch (B->ml) {
+      case 3: PATLD(3); break;
+      case 5: PATLD(5); break;
+      case 7: PATLD(7); break;
+      default: PATLD(8); break;
+      }
+      return;
+   }
    switch (B->ml) {
    case 3: PATL(3); break;
    case 5: PATL(5); break;
@@ -451,11 +555,12 @@ static void pat_launch_ml(const hipk_pat *B, hipStream_t st, int gx, const T *x,
    default: PATL(8); break;
    }
 #undef PATL
+#undef PATLD
 }
 
 /* y = A x (xout == NULL) or the fused form y = A (a x), xout = a x, partials[workgroup] = its part of xout'y
  * (a = 1/sqrt(norm2[0]), or of the sum of the np2 partial sums norm2[0 .. np2) when np2 > 0; norm2 == NULL: a = 1).
- * gx = hipk_pat_grid().  xlo / xhi: halo rows below / above the slab. */
+ * gx = hipk_pat_grid_kind(.., xout ? 1 : 0).  xlo / xhi: halo rows below / above the slab. */
 extern "C" int hipk_pat_matvec(const hipk_pat *B, void *hip_stream, int gx, const void *x, void *y, int64_t halo_lo, int64_t halo_hi,
       const void *xlo, const void *xhi, const double *norm2, int np2, void *xout, double *partials, const hipk_fin_args *fa_in) {
    hipStream_t st = (hipStream_t)hip_stream;
@@ -479,10 +584,23 @@ extern "C" int hipk_pat_matvec(const hipk_pat *B, void *hip_stream, int gx, cons
  * followed by the update.  yp may be NULL; out may be yp, never yk.  A slab without halo (the caller checks). */
 template <typename T>
 static void pat_cheb_launch(const hipk_pat *B, hipStream_t st, int gx, const double cf[4], const T *xr, const T *yk, const T *yp, T *out) {
-   const size_t shm = (size_t)B->npat * B->ml * 12 + (size_t)B->npat * 4 + 8;
+   const size_t shm = (size_t)B->npat * B->ml * 12 + (size_t)B->npat * (B->tds ? 8 : 4) + 8;
    const pat_cheb<T> ch = {cf[0], cf[1], cf[2], cf[3], xr, yp};
    hipk_fin_args fa;
    memset(&fa, 0, sizeof(fa));
+   if (B->tds) {
+      const pat_cheb_dg<T> cd = {cf[0], cf[1], cf[2], cf[3], xr, yp, (const T *)B->diag, B->tds};
+#define PATCD(MLV) hipLaunchKernelGGL((pat_kernel<T, MLV, PAT_RPL_FOR(MLV), pat_wps_diag(MLV, 2), false, false, true, true>), dim3(gx), dim3(HIPK_BLOCK), shm, st, B->pid, B->toff, B->tval, \
+         B->tlen, B->npat, B->nrows, yk, out, (int64_t)0, (const T *)NULL, (const T *)NULL, (const double *)NULL, 0, (T *)NULL, (double *)NULL, fa, B->minoff, B->maxoff, cd)
+      switch (B->ml) {
+      case 3: PATCD(3); break;
+      case 5: PATCD(5); break;
+      case 7: PATCD(7); break;
+      default: PATCD(8); break;
+      }
+#undef PATCD
+      return;
+   }
 #define PATC(MLV) hipLaunchKernelGGL((pat_kernel<T, MLV, PAT_RPL_FOR(MLV), HIPK_PAT_WPS, false, false, true>), dim3(gx), dim3(HIPK_BLOCK), shm, st, B->pid, B->toff, B->tval, \
          B->tlen, B->npat, B->nrows, yk, out, (int64_t)0, (const T *)NULL, (const T *)NULL, (const double *)NULL, 0, (T *)NULL, (double *)NULL, fa, B->minoff, B->maxoff, ch)
    switch (B->ml) {

@@ -53,6 +53,21 @@ def laplacian_csr(dims, row0=0, nrows=None, dtype=np.float64):
     return rowptr.astype(np.int32), cols, vals, n
 
 
+def schrodinger_csr(dims, potential, row0=0, nrows=None, dtype=np.float64):
+    """-Laplacian + V: laplacian_csr(dims, row0, nrows) with potential[i] added to the diagonal entry of global row i.
+    potential: an array over ALL n grid points, or a callable on the array of this slab's global row numbers.
+    Returns (rowptr, colind, values, n) like laplacian_csr; the sum is formed in double and rounded once to dtype."""
+    rp, ci, va, n = laplacian_csr(dims, row0, nrows, dtype=np.float64)
+    m = len(rp) - 1
+    g = np.arange(row0, row0 + m, dtype=np.int64)
+    v = np.asarray(potential(g) if callable(potential) else np.asarray(potential)[row0:row0 + m], dtype=np.float64)
+    if v.shape != (m,):
+        raise ValueError(f"potential: {m} values for rows [{row0}, {row0 + m}), got shape {v.shape}")
+    rows = np.repeat(g, np.diff(rp))
+    va[ci == rows] += v
+    return rp, ci, va.astype(dtype), n
+
+
 def laplacian_eigenvalues(dims, k):
     """k smallest analytic eigenvalues: sum_d 2 - 2cos(i_d pi/(n_d+1))."""
     axes = [2.0 - 2.0 * np.cos(np.arange(1, d + 1) * np.pi / (d + 1)) for d in dims if d >= 1]
