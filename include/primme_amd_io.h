@@ -19,6 +19,9 @@
  *                        (nothing allocated) when the matrix does not qualify: a row longer than 8, a 257th pattern,
  *                        two diagonal entries in a row, offsets out of reach
  *
+ *   primme_amd_csr_to_sliced             the sliced-ELL form (SELL-64-256) of the device operator created with HIPK_CSR_SLICED;
+ *                        layout at its declaration below
+ *
  * 0-based int32 indices; values double (complex: re, im interleaved).  Returned arrays are
  * malloc'ed by the library: release them with primme_amd_host_free.  Return 0 on success,
  * -1 cannot open, -2 malformed, -3 unsupported variant, -4 too large for int32, -5 out of memory. */
@@ -41,6 +44,35 @@ int primme_amd_csr_complex_to_real(int64_t n, const int32_t *rowptr, const int32
 int primme_amd_csr_row_patterns_diag(int64_t m, int64_t row0, const int32_t *rowptr, const int32_t *colind,
       const void *values, int is_float, uint8_t **pid, int *npat, int *ml, int32_t **len, int32_t **off,
       double **val, int32_t **dslot);
+/* Sliced-ELL form of a CSR matrix, SELL-64-256: what the device operator keeps beside the CSR arrays when it is created with
+ * HIPK_CSR_SLICED (primme_amd_kernels.h).
+ *   windows  256 consecutive rows; the rows of a window are sorted by descending length (stable) and become its SLOTS;
+ *            slot p of the matrix (window p / 256) holds row (p / 256) * 256 + perm[p] and that row's length len[p]
+ *   slices   64 consecutive slots; nslices = ceil(m / 64), the last window and the last slice may be ragged (slots >= m
+ *            have length 0).  Slice s is as wide as its longest row, width_s = (base[s + 1] - base[s]) / 64, and stores
+ *            entry j of its slot l at base[s] + 64 j + l: a row's entries in their CSR order, then padding
+ *   columns  idx16 = 1 (every slice's columns span less than 65 536): uint16 entries, column = cmin[s] + entry;
+ *            idx16 = 0: int32 entries, the columns themselves (cmin[s] = 0).  One width per matrix
+ *   padding  value 0 and a column some row of the matrix references; a product must skip it by the row's length (0 * x is
+ *            not 0 when x is NaN or Inf)
+ *   padded   sum over the slices of width_s * (slots of the slice that exist): the entries a product reads.  The form is
+ *            built when padded <= max_padding * nnz (the device operator asks for 1.25); the arrays hold base[nslices]
+ *            entries, the ragged last slice allocated 64 wide
+ * values: elem_size bytes each, copied bit for bit.  Returns 0 and *S (release with primme_amd_sliced_free), 1 when the
+ * padding is above the limit or the matrix has no entry (nothing allocated), -4 a row longer than 65 535, -5 out of memory. */
+typedef struct primme_amd_sliced {
+   int64_t m, nnz, nslices, padded;
+   int idx16;
+   int64_t *base;        /* nslices + 1 */
+   int32_t *cmin;        /* nslices */
+   uint8_t *perm;        /* 64 nslices */
+   uint16_t *len;        /* 64 nslices */
+   void *val;            /* base[nslices] elements */
+   void *idx;            /* base[nslices] uint16 / int32 */
+} primme_amd_sliced;
+int primme_amd_csr_to_sliced(int64_t m, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
+      double max_padding, primme_amd_sliced **S);
+void primme_amd_sliced_free(primme_amd_sliced *S);
 void primme_amd_host_free(void *p);
 #ifdef __cplusplus
 }

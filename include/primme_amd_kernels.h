@@ -349,6 +349,19 @@ int hipk_csr_create(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local, int64_t n
  * entry; the diagonal's value is streamed per row from hipk_csr_diag: stencil / lattice operator + potential, on-site
  * disorder, graded shifts.  hipk_csr_create takes its flags from HIPK_SPMV_PAT_DIAG=1 in the environment (default: none). */
 #define HIPK_CSR_DIAG_PATTERNS 1u
+/* HIPK_CSR_SLICED: a general matrix (FEM, graph, structural: neither the row-pattern nor the panel-blocked form takes it) also
+ * gets a SLICED-ELL form, SELL-64-256 (csrc/hipk_sparse_sell.hip; layout: primme_amd_io.h): rows sorted by length inside windows
+ * of 256, slices of 64 slots stored column-major, 16-bit column offsets when every slice spans fewer than 65 536 columns.
+ * hipk_csr_matvec and hipk_csr_matvec_shifted then run one lane per row with coalesced loads from HBM to registers and no LDS
+ * staging; every column is one fma chain in row order (the result of a column does not depend on the width of the call and
+ * is the same from run to run; it differs from the row tiles' in the last bits).  Covered: real, square row slabs without
+ * halo (single rank, block-diagonal partitions).  Built only when the padded entries are <= 1.25 nnz; otherwise, and for any
+ * operator not covered, the flag is accepted and the operator is exactly what it is without it.  The CSR arrays stay on the
+ * device — hipk_csr_cheb_step, hipk_csr_matvec_scaled, hipk_csr_gershgorin, hipk_csr_abs_rowsum_max and hipk_csr_diag use
+ * them unchanged — so the form COSTS padded * (s + 2 or 4) bytes + 3 per row more device memory.  Both flags may be set.
+ * hipk_csr_create takes it from HIPK_SPMV_SELL=1 in the environment.  hipk_set_spmv_format(0) switches back to the row tiles
+ * at run time on the same handle. */
+#define HIPK_CSR_SLICED 2u
 int hipk_csr_create_opts(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local, int64_t ncols_global,
       int64_t row0, const int32_t *rowptr_host, const int32_t *colind_host,
       const void *values_host, unsigned flags, hipk_csr **A);
@@ -456,7 +469,7 @@ double hipk_csr_streamed_bytes(const hipk_csr *A);
  * bit-identical; the fused form's inner product differs in summation order only).  HIPK_SPMV_PAT=0 in the
  * environment, or hipk_set_spmv_format(0) at run time, keeps the CSR tile kernels (A/B measurements, tests); returns
  * the previous setting.  hipk_csr_format: the form that serves one-column products now (0 CSR row tiles, 1
- * panel-blocked, 2 row patterns, 3 stencil); hipk_csr_product_bytes: the bytes one such product moves through HBM in
+ * panel-blocked, 2 row patterns, 3 stencil, 4 sliced ELL); hipk_csr_product_bytes: the bytes one such product moves through HBM in
  * that form (fused: with the second output of hipk_csr_matvec_scaled) — what "streamed bytes" means in bench.py. */
 int hipk_set_spmv_format(int use_patterns);
 int hipk_csr_format(const hipk_csr *A);
@@ -464,6 +477,11 @@ int hipk_csr_npatterns(const hipk_csr *A);
 /* 1 when the form in use is the diagonal-split flavour of the row patterns (HIPK_CSR_DIAG_PATTERNS; hipk_csr_format is 2 for
  * both flavours): the product then streams the diagonal as well, nrows (1 + 3 s) bytes, nrows (1 + 4 s) fused */
 int hipk_csr_pattern_diag(const hipk_csr *A);
+/* hipk_csr_sliced: 1 when the sliced-ELL form was built (HIPK_CSR_SLICED), whether or not hipk_set_spmv_format has it switched
+ * on; hipk_csr_sliced_padding: its padded entries / nnz (0 without the form).  While it serves the products hipk_csr_format
+ * is 4 and hipk_csr_product_bytes(A, 0) / hipk_csr_streamed_bytes are padded * (s + 2 or 4) + 204 per slice + 2 nrows s. */
+int hipk_csr_sliced(const hipk_csr *A);
+double hipk_csr_sliced_padding(const hipk_csr *A);
 double hipk_csr_product_bytes(const hipk_csr *A, int fused);
 /* Second stage of the reductions of the block-size-1 iteration: bit 1 fused residual pass, 2 Gram-Schmidt update, 4 fused
  * SpMV run it inside the producing launch (two-level, write-through partial sums, csrc/hipk_internal.h); 0 = a separate

@@ -323,16 +323,27 @@ def declare_formats(lib):
     P = C.POINTER
     lib.hipk_csr_create_opts.argtypes = [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, C.c_uint, P(_vp)]
     lib.hipk_csr_create_opts.restype = C.c_int
-    for name in ("hipk_csr_format", "hipk_csr_npatterns", "hipk_csr_pattern_diag"):
+    for name in ("hipk_csr_format", "hipk_csr_npatterns", "hipk_csr_pattern_diag", "hipk_csr_sliced"):
         getattr(lib, name).argtypes = [_vp]
         getattr(lib, name).restype = C.c_int
     lib.hipk_set_spmv_format.argtypes = [_i]
     lib.hipk_set_spmv_format.restype = C.c_int
     lib.hipk_csr_product_bytes.argtypes = [_vp, _i]
     lib.hipk_csr_product_bytes.restype = C.c_double
+    for name in ("hipk_csr_sliced_padding", "hipk_csr_streamed_bytes"):
+        getattr(lib, name).argtypes = [_vp]
+        getattr(lib, name).restype = C.c_double
 
 
 HIPK_CSR_DIAG_PATTERNS = 1
+HIPK_CSR_SLICED = 2
+
+
+class PrimmeAmdSliced(C.Structure):
+    """primme_amd_sliced of include/primme_amd_io.h: the sliced-ELL form primme_amd_csr_to_sliced returns"""
+    _fields_ = [("m", C.c_int64), ("nnz", C.c_int64), ("nslices", C.c_int64), ("padded", C.c_int64), ("idx16", C.c_int),
+                ("base", C.POINTER(C.c_int64)), ("cmin", C.POINTER(C.c_int32)), ("perm", C.POINTER(C.c_uint8)),
+                ("len", C.POINTER(C.c_uint16)), ("val", C.c_void_p), ("idx", C.c_void_p)]
 
 _cache = {}
 

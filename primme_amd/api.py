@@ -21,11 +21,16 @@ class Operator:
 
     diag_patterns=True (real CSR matrices): when the rows repeat but for their diagonal entry (stencil or lattice operator +
     potential / on-site term), the device keeps one byte per row and streams the diagonal (HIPK_CSR_DIAG_PATTERNS of
-    hipk_csr_create_opts) instead of the CSR arrays for the one-column products; same results, fewer bytes."""
+    hipk_csr_create_opts) instead of the CSR arrays for the one-column products; same results, fewer bytes.
 
-    def __init__(self, n, csr=None, stencil=None, row0=0, nrows=None, diag_patterns=False):
+    sliced=True (real CSR matrices without halo): a general matrix also gets the sliced-ELL form (HIPK_CSR_SLICED) that serves
+    the plain and the shifted products of any width, when its padding stays within 1.25 nnz; the CSR arrays stay on the device
+    beside it.  Results agree with the row tiles' to rounding.  Both keywords may be set."""
+
+    def __init__(self, n, csr=None, stencil=None, row0=0, nrows=None, diag_patterns=False, sliced=False):
         self.n = int(n)
         self.diag_patterns = bool(diag_patterns)
+        self.sliced = bool(sliced)
         self.csr = csr            # (rowptr int32, colind int32, values)
         self.stencil = stencil    # (nx, ny, nz)
         self.row0 = int(row0)
@@ -142,11 +147,13 @@ class Session:
                 for h in (rp2, ci2, va2): lib.primme_amd_host_free(h)
             else:
                 va = np.ascontiguousarray(va, dtype=self.dtype)
-                if getattr(op, "diag_patterns", False) and self.be.device:
+                flags = ((F.HIPK_CSR_DIAG_PATTERNS if getattr(op, "diag_patterns", False) else 0) |
+                         (F.HIPK_CSR_SLICED if getattr(op, "sliced", False) else 0))
+                if flags and self.be.device:
                     # the form of the device operator only: a checker that runs the host solver over host vectors has one form
                     rc = lib.hipk_csr_create_opts(ctx, self.dt, op.nrows, op.n, op.row0, rp.ctypes.data_as(C.c_void_p),
                                                   ci.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p),
-                                                  F.HIPK_CSR_DIAG_PATTERNS, C.byref(A))
+                                                  flags, C.byref(A))
                 else:
                     rc = lib.hipk_csr_create(ctx, self.dt, op.nrows, op.n, op.row0, rp.ctypes.data_as(C.c_void_p),
                                              ci.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p), C.byref(A))

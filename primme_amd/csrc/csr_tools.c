@@ -254,3 +254,91 @@ int primme_amd_csr_row_patterns_diag(int64_t m, int64_t row0, const int32_t *rp,
    *pid_out = pid; *npat_out = npat; *ml_out = ml; *len_out = tlen; *off_out = toff; *val_out = tval; *dslot_out = tds;
    return 0;
 }
+
+/* Sliced-ELL form of a CSR matrix, SELL-64-256 (device: hipk_sparse_sell.hip; layout: include/primme_amd_io.h).  Rows are
+ * sorted by descending length inside windows of 256 consecutive rows (stable: equal lengths keep their order), the sorted
+ * rows are the SLOTS, 64 consecutive slots are a SLICE, and a slice stores its entries column-major, padded to its longest
+ * row.  Returns 0 and the form;  1 (nothing allocated) when the padded entries exceed max_padding * nnz or the matrix is
+ * empty;  -4 when a row is longer than 65 535 entries;  -5 out of memory. */
+void primme_amd_sliced_free(primme_amd_sliced *S) {
+   if (!S) return;
+   free(S->base); free(S->cmin); free(S->perm); free(S->len); free(S->val); free(S->idx);
+   free(S);
+}
+
+int primme_amd_csr_to_sliced(int64_t m, const int32_t *rp, const int32_t *ci, const void *values, size_t elem_size,
+      double max_padding, primme_amd_sliced **out) {
+   *out = NULL;
+   if (m <= 0 || rp[m] <= 0) return 1;
+   const int64_t nnz = rp[m], nslices = (m + 63) / 64, nslots = nslices * 64;
+   primme_amd_sliced *S = (primme_amd_sliced *)calloc(1, sizeof *S);
+   if (!S) return -5;
+   S->m = m; S->nnz = nnz; S->nslices = nslices;
+   S->base = (int64_t *)calloc((size_t)nslices + 1, sizeof(int64_t));
+   S->cmin = (int32_t *)calloc((size_t)nslices, sizeof(int32_t));
+   S->perm = (uint8_t *)calloc((size_t)nslots, 1);
+   S->len = (uint16_t *)calloc((size_t)nslots, sizeof(uint16_t));
+   int32_t *start = (int32_t *)malloc(sizeof(int32_t) * 65538);
+   if (!S->base || !S->cmin || !S->perm || !S->len || !start) { free(start); primme_amd_sliced_free(S); return -5; }
+   /* the slots: a counting sort by length inside every window keeps equal lengths in row order */
+   for (int64_t w0 = 0; w0 < m; w0 += 256) {
+      const int nr = (int)(m - w0 < 256 ? m - w0 : 256);
+      int maxlen = 0;
+      for (int r = 0; r < nr; r++) {
+         const int64_t len = (int64_t)rp[w0 + r + 1] - rp[w0 + r];
+         if (len < 0 || len > 65535) { free(start); primme_amd_sliced_free(S); return -4; }
+         if (len > maxlen) maxlen = (int)len;
+      }
+      /* start[len] = first slot of the rows of that length, longest first; rows then take their slots in row order */
+      memset(start, 0, sizeof(int32_t) * ((size_t)maxlen + 2));
+      for (int r = 0; r < nr; r++) start[rp[w0 + r + 1] - rp[w0 + r]]++;
+      for (int len = maxlen, k = 0; len >= 0; len--) { const int c = start[len]; start[len] = k; k += c; }
+      for (int r = 0; r < nr; r++) {
+         const int len = rp[w0 + r + 1] - rp[w0 + r], k = start[len]++;
+         S->perm[w0 + k] = (uint8_t)r; S->len[w0 + k] = (uint16_t)len;
+      }
+   }
+   free(start);
+   /* widths, bases, column spans; padded counts the entries of the slots that exist (the ragged last slice is ALLOCATED
+    * 64 wide like the others, so that slot l's entry j is at base + 64 j + l everywhere) */
+   int64_t padded = 0, span_max = 0;
+   for (int64_t s = 0; s < nslices; s++) {
+      const int ns = (int)(m - s * 64 < 64 ? m - s * 64 : 64);
+      const int width = S->len[s * 64];                     /* sorted: the slice's first slot is its longest row */
+      int64_t lo = INT64_MAX, hi = -1;
+      for (int l = 0; l < ns; l++) {
+         const int64_t row = (s * 64 / 256) * 256 + S->perm[s * 64 + l];
+         for (int32_t p = rp[row]; p < rp[row + 1]; p++) { if (ci[p] < lo) lo = ci[p]; if (ci[p] > hi) hi = ci[p]; }
+      }
+      S->cmin[s] = hi >= lo ? (int32_t)lo : 0;
+      if (hi >= lo && hi - lo > span_max) span_max = hi - lo;
+      S->base[s + 1] = S->base[s] + (int64_t)width * 64;
+      padded += (int64_t)width * ns;
+   }
+   S->padded = padded;
+   if ((double)padded > max_padding * (double)nnz) { primme_amd_sliced_free(S); return 1; }
+   S->idx16 = span_max < 65536;
+   const size_t is = S->idx16 ? 2 : 4;
+   const int64_t total = S->base[nslices];
+   S->val = calloc((size_t)(total > 0 ? total : 1), elem_size);
+   S->idx = calloc((size_t)(total > 0 ? total : 1), is);
+   if (!S->val || !S->idx) { primme_amd_sliced_free(S); return -5; }
+   if (!S->idx16) for (int64_t s = 0; s < nslices; s++) S->cmin[s] = 0;      /* 32-bit entries are the columns themselves */
+   /* padding: value 0 (calloc) and the slice's first column (entry 0 against cmin), or, 32-bit, a column of the matrix */
+   const int32_t anycol = ci[0];
+   if (!S->idx16) for (int64_t q = 0; q < total; q++) ((int32_t *)S->idx)[q] = anycol;
+   for (int64_t s = 0; s < nslices; s++) {
+      const int ns = (int)(m - s * 64 < 64 ? m - s * 64 : 64);
+      for (int l = 0; l < ns; l++) {
+         const int64_t row = (s * 64 / 256) * 256 + S->perm[s * 64 + l];
+         for (int j = 0; j < S->len[s * 64 + l]; j++) {
+            const int64_t q = S->base[s] + (int64_t)j * 64 + l, p = (int64_t)rp[row] + j;
+            memcpy((char *)S->val + (size_t)q * elem_size, (const char *)values + (size_t)p * elem_size, elem_size);
+            if (S->idx16) ((uint16_t *)S->idx)[q] = (uint16_t)(ci[p] - S->cmin[s]);
+            else ((int32_t *)S->idx)[q] = ci[p];
+         }
+      }
+   }
+   *out = S;
+   return 0;
+}

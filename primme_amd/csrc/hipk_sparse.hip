@@ -47,9 +47,17 @@ struct hipk_csr {
    int sx, sy, sz;             /* stencil grid */
    struct hipk_pb *pb;         /* panel-blocked form (hipk_sparse_pb.hip) for scattered column patterns, or NULL */
    struct hipk_pat *pat;       /* row-pattern dictionary form (hipk_sparse_pat.hip) for matrices whose rows repeat, or NULL */
+   struct hipk_sell *sell;     /* sliced-ELL form (hipk_sparse_sell.hip), built on request (HIPK_CSR_SLICED) beside the CSR arrays, or NULL */
 };
 struct hipk_pb;
 struct hipk_pat;
+struct hipk_sell;
+extern "C" int hipk_sell_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const int32_t *rp, const int32_t *ci, const void *val, hipk_sell **out);
+extern "C" void hipk_sell_destroy(hipk_sell *B);
+extern "C" double hipk_sell_padding(const hipk_sell *B);
+extern "C" double hipk_sell_bytes(const hipk_sell *B, int ncols);
+extern "C" int hipk_sell_matvec(const hipk_sell *B, void *hip_stream, int64_t row0, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols,
+      const double *shift_host);
 extern "C" int hipk_pat_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t row0, const int32_t *rp, const int32_t *ci, const void *val, hipk_pat **out);
 extern "C" int hipk_pat_build_diag(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t row0, const int32_t *rp, const int32_t *ci, const void *val,
       const void *diag_dev, hipk_pat **out);
@@ -717,6 +725,14 @@ static int csr_create_impl(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local,
          if (rcd < 0) return rcd;
       }
    }
+   /* HIPK_CSR_SLICED: a general matrix (neither of the forms above took it) whose rows and input entries coincide and are
+    * all local also gets the sliced-ELL form, when its padding stays within 1.25 nnz (hipk_sparse_sell.hip); anything
+    * else keeps the row tiles alone */
+   if ((flags & HIPK_CSR_SLICED) && (dt == HIPK_F64 || dt == HIPK_F32) && lo == 0 && hi == 0 && x0 == row0 && xlen == nrows_local &&
+         ncols_global >= row0 + nrows_local && !A->pb && !A->pat) {
+      const int rcs = hipk_sell_build(ctx, dt, nrows_local, rowptr_host, colind_host, values_host, &A->sell);
+      if (rcs < 0) return rcs;
+   }
    *out = A;
    return 0;
 }
@@ -727,13 +743,14 @@ extern "C" int hipk_csr_create_opts(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_
    return csr_create_impl(ctx, dt, nrows_local, ncols_global, row0, row0, nrows_local, rowptr_host,
          colind_host, values_host, flags, out);
 }
-/* the flags of hipk_csr_create: HIPK_SPMV_PAT_DIAG=1 in the environment asks for the diagonal-split row patterns (default: none) */
+/* the flags of hipk_csr_create: HIPK_SPMV_PAT_DIAG=1 in the environment asks for the diagonal-split row patterns,
+ * HIPK_SPMV_SELL=1 for the sliced-ELL form (default: none) */
 extern "C" int hipk_csr_create(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows_local,
       int64_t ncols_global, int64_t row0, const int32_t *rowptr_host,
       const int32_t *colind_host, const void *values_host, hipk_csr **out) {
-   const char *e = getenv("HIPK_SPMV_PAT_DIAG");
+   const char *e = getenv("HIPK_SPMV_PAT_DIAG"), *s = getenv("HIPK_SPMV_SELL");
    return hipk_csr_create_opts(ctx, dt, nrows_local, ncols_global, row0, rowptr_host, colind_host, values_host,
-         (e && atoi(e) != 0) ? HIPK_CSR_DIAG_PATTERNS : 0u, out);
+         ((e && atoi(e) != 0) ? HIPK_CSR_DIAG_PATTERNS : 0u) | ((s && atoi(s) != 0) ? HIPK_CSR_SLICED : 0u), out);
 }
 extern "C" int hipk_csr_create_rect(hipk_ctx *ctx, hipk_dtype dt, int64_t nrows, int64_t ncols,
       const int32_t *rowptr_host, const int32_t *colind_host, const void *values_host, hipk_csr **out) {
@@ -783,6 +800,7 @@ extern "C" int hipk_csr_destroy(hipk_csr *A) {
    if (A->diag) (void)hipFree(A->diag);
    if (A->pb) hipk_pb_destroy(A->pb);
    if (A->pat) hipk_pat_destroy(A->pat);
+   if (A->sell) hipk_sell_destroy(A->sell);
    free(A);
    return 0;
 }
@@ -812,13 +830,20 @@ extern "C" int hipk_csr_index_bytes(const hipk_csr *A) { return (A && A->kind ==
 
 /* number of column panels of the panel-blocked form (0: plain CSR kernels serve this matrix) */
 extern "C" int hipk_csr_panels(const hipk_csr *A) { return A && A->pb ? hipk_pb_panels(A->pb) : 0; }
-/* the form that serves the ONE-column products of this matrix right now: 0 CSR row tiles, 1 panel-blocked, 2 row patterns, 3 stencil */
+/* the sliced-ELL form serves hipk_csr_matvec / hipk_csr_matvec_shifted now: built, and not switched off by hipk_set_spmv_format(0) */
+static bool csr_sell_on(const hipk_csr *A) { return A->sell && hipk_pat_enabled(); }
+/* the form that serves the ONE-column products of this matrix right now: 0 CSR row tiles, 1 panel-blocked, 2 row patterns, 3 stencil,
+ * 4 sliced ELL */
 extern "C" int hipk_csr_format(const hipk_csr *A) {
    if (!A) return -1;
    if (A->kind == 1) return 3;
    if (A->pat && hipk_pat_enabled()) return 2;
+   if (csr_sell_on(A)) return 4;
    return A->pb ? 1 : 0;
 }
+/* 1 when the sliced-ELL form was built (whether or not it is switched on right now); its padded entries / nnz, 0 without it */
+extern "C" int hipk_csr_sliced(const hipk_csr *A) { return A && A->sell ? 1 : 0; }
+extern "C" double hipk_csr_sliced_padding(const hipk_csr *A) { return A && A->sell ? hipk_sell_padding(A->sell) : 0.0; }
 extern "C" int hipk_csr_npatterns(const hipk_csr *A) { return A && A->pat ? hipk_pat_npatterns(A->pat) : 0; }
 /* 1 when the form in use is the row-pattern form in its diagonal-split flavour (the product streams the diagonal) */
 extern "C" int hipk_csr_pattern_diag(const hipk_csr *A) { return hipk_csr_format(A) == 2 && hipk_pat_diag(A->pat); }
@@ -831,10 +856,15 @@ extern "C" double hipk_csr_product_bytes(const hipk_csr *A, int fused) {
    case 3: return vec;
    case 2: return hipk_pat_bytes(A->pat, fused);
    case 1: return hipk_pb_bytes(A->pb) + (fused ? (double)A->nrows * es : 0.0);
+   case 4: if (!fused) return hipk_sell_bytes(A->sell, 1);      /* the fused product stays on the row tiles */
+      /* fall through */
    default: return (double)A->nnz * (es + hipk_csr_index_bytes(A)) + (A->nrows + 1) * 4.0 + vec;
    }
 }
-extern "C" double hipk_csr_streamed_bytes(const hipk_csr *A) { return A && A->pb ? hipk_pb_bytes(A->pb) : 0.0; }
+extern "C" double hipk_csr_streamed_bytes(const hipk_csr *A) {
+   if (A && A->kind == 0 && csr_sell_on(A)) return hipk_sell_bytes(A->sell, 1);
+   return A && A->pb ? hipk_pb_bytes(A->pb) : 0.0;
+}
 
 /* stream the matrix past the Infinity Cache?  Yes when its (value, index) stream alone is more than about three quarters
  * of the 256 MiB (it cannot stay until the next product anyway); HIPK_SPMV_NT=0 / 1 forces it (A/B knob) */
@@ -866,13 +896,20 @@ static int csr_matvec_t(hipk_csr *A, hipStream_t stream, const T *x, int64_t ldx
    if (A->kind == 0) {
       const bool one_pat = A->pat && hipk_pat_enabled() && ncols == 1 && !shift_host && !cheb;
       const bool one_pb = A->pb && !shift_host && !cheb && ncols <= pb_maxcols;
+      const bool one_sell = csr_sell_on(A) && !cheb;
       const bool win = A->halo_lo == 0 && A->halo_hi == 0 && ncols <= 64 && ((A->windowed && ncols >= 2) || shift_host || cheb);
-      if (one_pat) streamed = hipk_pat_bytes(A->pat, 0);
+      if (one_sell) streamed = hipk_sell_bytes(A->sell, ncols);
+      else if (one_pat) streamed = hipk_pat_bytes(A->pat, 0);
       else if (one_pb) streamed = hipk_pb_bytes(A->pb) * ncols;
       else streamed = (double)A->nnz * (es + ((win || ncols == 1) && csr16(A) ? 2 : 4)) + (A->nrows + 1) * 4.0 + 2.0 * A->nrows * es * ncols;
    }
    if (cheb) streamed += ((cheb->yp ? 2.0 : 1.0) + (cheb->yk && cheb->yk != x ? 1.0 : 0.0)) * A->nrows * es * ncols;      /* the epilogue's other panels */
    const int pslot = hipk_prof_begin_s(HIPK_PROF_SPMV, stream, cheb ? streamed : alg, streamed);
+   if (A->kind == 0 && csr_sell_on(A) && !cheb) {      /* plain and shifted products, any width (never together with pat / pb) */
+      const int rc = hipk_sell_matvec(A->sell, stream, A->row0, x, ldx, y, ldy, ncols, shift_host);
+      hipk_prof_end(pslot, stream);
+      return rc;
+   }
    if (A->pat && hipk_pat_enabled() && ncols == 1 && !shift_host && !cheb) {
       const int rc = hipk_pat_matvec(A->pat, stream, hipk_pat_grid(A->pat, ctx->num_cu), x, y, A->halo_lo, A->halo_hi, A->xlo, A->xhi, NULL, 0, NULL,
             NULL, NULL);
