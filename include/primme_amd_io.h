@@ -21,6 +21,8 @@
  *
  *   primme_amd_csr_to_sliced             the sliced-ELL form (SELL-64-256) of the device operator created with HIPK_CSR_SLICED;
  *                        layout at its declaration below
+ *   primme_amd_csr_tile_plan             the host analysis of the device CSR operator's row-tile kernels: tiles, column
+ *                        windows, halo extent, diagonal and the 16-bit index stream; fields at its declaration below
  *
  * 0-based int32 indices; values double (complex: re, im interleaved).  Returned arrays are
  * malloc'ed by the library: release them with primme_amd_host_free.  Return 0 on success,
@@ -73,6 +75,35 @@ typedef struct primme_amd_sliced {
 int primme_amd_csr_to_sliced(int64_t m, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
       double max_padding, primme_amd_sliced **S);
 void primme_amd_sliced_free(primme_amd_sliced *S);
+/* Row tiles of the device CSR operator (hipk_csr_create*): what its tile kernels are launched over.  The limits are shared
+ * with the kernels: a tile holds at most PRIMME_AMD_TILE_NNZ nonzeros and PRIMME_AMD_TILE_ROWS consecutive rows (greedy; a
+ * single longer row is a tile of its own), a column window at most PRIMME_AMD_TILE_WINDOW columns.
+ *   rows [row0, row0 + nrows) of the matrix; entries [x0, x0 + xlen) of the input vector are owned, others are halo
+ *   tiles    ntiles + 1 row offsets;  info: {first row, end row, first nonzero, end nonzero} per tile;  win: {first column,
+ *            width} of the tile's columns when they lie inside the owned entries and span at most the window limit, else
+ *            {0, 0}.  info and win hold one more, zero, record
+ *   cw_max   the widest window;  windowed: no halo and at least 9 tiles in 10 have a window with 8 width <= the limit
+ *   halo_lo / halo_hi   how far the columns reach below x0 / beyond x0 + xlen;  diag: the entry at column row0 + i of
+ *            row i (0 without one), nrows elements of elem_size bytes
+ *   col16    real_values only, else NULL: column - (row0 + first row of the tile - c16back) for every nonzero (+ one zero
+ *            entry), c16back = the farthest a tile's columns reach below its first row; NULL when an entry would exceed
+ *            65 535 or row0 - c16back / ncols_global leave the int32 range the kernels compute in
+ * Returns 0 and *P (release with primme_amd_tile_plan_free), -5 out of memory. */
+#define PRIMME_AMD_TILE_NNZ 2048
+#define PRIMME_AMD_TILE_ROWS 256
+#define PRIMME_AMD_TILE_WINDOW 3072
+typedef struct primme_amd_tile_plan {
+   int ntiles, cw_max, windowed;
+   int64_t halo_lo, halo_hi, c16back;
+   int32_t *tiles;       /* ntiles + 1 */
+   int32_t *info;        /* 4 (ntiles + 1) */
+   int32_t *win;         /* 2 (ntiles + 1) */
+   void *diag;           /* nrows elements */
+   uint16_t *col16;      /* nnz + 1, or NULL */
+} primme_amd_tile_plan;
+int primme_amd_csr_tile_plan(int64_t nrows, int64_t row0, int64_t x0, int64_t xlen, int64_t ncols_global, const int32_t *rowptr,
+      const int32_t *colind, const void *values, size_t elem_size, int real_values, primme_amd_tile_plan **P);
+void primme_amd_tile_plan_free(primme_amd_tile_plan *P);
 void primme_amd_host_free(void *p);
 #ifdef __cplusplus
 }

@@ -345,6 +345,12 @@ class PrimmeAmdSliced(C.Structure):
                 ("base", C.POINTER(C.c_int64)), ("cmin", C.POINTER(C.c_int32)), ("perm", C.POINTER(C.c_uint8)),
                 ("len", C.POINTER(C.c_uint16)), ("val", C.c_void_p), ("idx", C.c_void_p)]
 
+class PrimmeAmdTilePlan(C.Structure):
+    """primme_amd_tile_plan of include/primme_amd_io.h: the row tiles primme_amd_csr_tile_plan returns"""
+    _fields_ = [("ntiles", C.c_int), ("cw_max", C.c_int), ("windowed", C.c_int), ("halo_lo", C.c_int64), ("halo_hi", C.c_int64),
+                ("c16back", C.c_int64), ("tiles", C.POINTER(C.c_int32)), ("info", C.POINTER(C.c_int32)), ("win", C.POINTER(C.c_int32)),
+                ("diag", C.c_void_p), ("col16", C.POINTER(C.c_uint16))]
+
 _cache = {}
 
 

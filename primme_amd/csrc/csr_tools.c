@@ -6,6 +6,7 @@
  *   primme_amd_csr_tile_block_diagonal  the tiler that builds BASELINE configs[2] from LUNDA.mtx
  *   primme_amd_csr_transpose      explicit A' for the singular value operator
  *   primme_amd_csr_complex_to_real  Hermitian matrix -> symmetric real-equivalent form
+ *   primme_amd_csr_tile_plan      the row tiles, column windows and 16-bit index stream of the device CSR operator
  *
  * Indices are 0-based int32 (the device kernels' format); values are double, complex as
  * (re, im) pairs.  Everything returned is malloc'ed; release with primme_amd_host_free. */
@@ -340,5 +341,95 @@ int primme_amd_csr_to_sliced(int64_t m, const int32_t *rp, const int32_t *ci, co
       }
    }
    *out = S;
+   return 0;
+}
+
+/* The host analysis of the row-tile kernels (device: hipk_sparse.hip, hipk_complex.hip; fields: include/primme_amd_io.h).
+ * Consecutive rows are binned greedily into tiles of at most PRIMME_AMD_TILE_NNZ nonzeros and PRIMME_AMD_TILE_ROWS rows, a
+ * single longer row is a tile of its own.  One pass over the rows gives the halo extent and the diagonal, one pass over every
+ * tile its column window.  Returns 0 and *out, -5 out of memory. */
+void primme_amd_tile_plan_free(primme_amd_tile_plan *P) {
+   if (!P) return;
+   free(P->tiles); free(P->info); free(P->win); free(P->diag); free(P->col16);
+   free(P);
+}
+
+int primme_amd_csr_tile_plan(int64_t nrows, int64_t row0, int64_t x0, int64_t xlen, int64_t ncols_global, const int32_t *rp,
+      const int32_t *ci, const void *values, size_t elem_size, int real_values, primme_amd_tile_plan **out) {
+   *out = NULL;
+   primme_amd_tile_plan *P = (primme_amd_tile_plan *)calloc(1, sizeof *P);
+   if (!P) return -5;
+   /* at most one tile per row; the records and windows carry one zero element behind the last tile */
+   P->tiles = (int32_t *)calloc((size_t)nrows + 1, sizeof(int32_t));
+   P->diag = calloc((size_t)(nrows > 0 ? nrows : 1), elem_size);
+   if (!P->tiles || !P->diag) { primme_amd_tile_plan_free(P); return -5; }
+   int64_t r = 0;
+   int nt = 0;
+   while (r < nrows) {
+      const int64_t rs = r;
+      int64_t cnt = 0;
+      while (r < nrows && (r - rs) < PRIMME_AMD_TILE_ROWS) {
+         const int64_t rn = rp[r + 1] - rp[r];
+         if (cnt + rn > PRIMME_AMD_TILE_NNZ && r > rs) break;
+         cnt += rn;
+         r++;
+         if (cnt > PRIMME_AMD_TILE_NNZ) break;         /* a single long row forms its own tile */
+      }
+      P->tiles[++nt] = (int32_t)r;
+   }
+   P->ntiles = nt;
+   int64_t lo = 0, hi = 0;
+   for (int64_t i = 0; i < nrows; i++)
+      for (int32_t p = rp[i]; p < rp[i + 1]; p++) {
+         const int64_t g = ci[p];
+         if (g < x0 && x0 - g > lo) lo = x0 - g;
+         if (g >= x0 + xlen && g - (x0 + xlen) + 1 > hi) hi = g - (x0 + xlen) + 1;
+         if (g == row0 + i) memcpy((char *)P->diag + (size_t)i * elem_size, (const char *)values + (size_t)p * elem_size, elem_size);
+      }
+   P->halo_lo = lo; P->halo_hi = hi;
+   P->info = (int32_t *)calloc(4 * ((size_t)nt + 1), sizeof(int32_t));
+   P->win = (int32_t *)calloc(2 * ((size_t)nt + 1), sizeof(int32_t));
+   int64_t *tmax = (int64_t *)malloc(sizeof(int64_t) * ((size_t)nt + 1));      /* last column of every tile, -1: no entry */
+   if (!P->info || !P->win || !tmax) { free(tmax); primme_amd_tile_plan_free(P); return -5; }
+   /* back = the farthest any tile reaches below its first row, reach = the farthest above (first row - back) */
+   int64_t narrow = 0, back = 0, reach = 0;
+   for (int t = 0; t < nt; t++) {
+      const int32_t r0 = P->tiles[t], r1 = P->tiles[t + 1];
+      int32_t *ti = P->info + 4 * (size_t)t;
+      ti[0] = r0; ti[1] = r1; ti[2] = rp[r0]; ti[3] = rp[r1];
+      int64_t cmin = INT64_MAX, cmax = -1;
+      for (int32_t p = rp[r0]; p < rp[r1]; p++) {
+         const int64_t g = ci[p];
+         if (g < cmin) cmin = g;
+         if (g > cmax) cmax = g;
+      }
+      tmax[t] = cmax;
+      if (cmax >= cmin && row0 + r0 - cmin > back) back = row0 + r0 - cmin;
+      /* the shifted product also reads x at the tile's own rows: they are local by construction */
+      const int64_t width = cmax - cmin + 1;
+      if (cmax >= cmin && cmin >= x0 && cmax < x0 + xlen && width <= PRIMME_AMD_TILE_WINDOW) {
+         P->win[2 * (size_t)t] = (int32_t)cmin; P->win[2 * (size_t)t + 1] = (int32_t)width;
+         if ((int)width > P->cw_max) P->cw_max = (int)width;
+         if (width * 8 <= PRIMME_AMD_TILE_WINDOW) narrow++;
+      }
+   }
+   P->windowed = (lo == 0 && hi == 0 && nt > 0 && narrow * 10 >= (int64_t)nt * 9);
+   /* A second, 2-byte index stream when the pattern allows it: entry = column - (row0 + first row of the tile - c16back).
+    * 10 instead of 12 bytes per nonzero out of HBM for a double matrix; the tile kernels rebuild the column from the tile
+    * record they load anyway. */
+   if (real_values && nt > 0) {
+      for (int t = 0; t < nt; t++)
+         if (rp[P->tiles[t + 1]] > rp[P->tiles[t]] && tmax[t] - (row0 + P->tiles[t] - back) > reach) reach = tmax[t] - (row0 + P->tiles[t] - back);
+      if (reach <= 65535 && row0 - back > (int64_t)INT32_MIN / 2 && ncols_global < (int64_t)INT32_MAX) {
+         P->col16 = (uint16_t *)calloc((size_t)rp[nrows] + 1, sizeof(uint16_t));      /* +1: clamped loads of an empty tile */
+         if (!P->col16) { free(tmax); primme_amd_tile_plan_free(P); return -5; }
+         P->c16back = back;
+         for (int t = 0; t < nt; t++)
+            for (int32_t p = rp[P->tiles[t]]; p < rp[P->tiles[t + 1]]; p++)
+               P->col16[p] = (uint16_t)(ci[p] - (row0 + P->tiles[t] - back));
+      }
+   }
+   free(tmax);
+   *out = P;
    return 0;
 }

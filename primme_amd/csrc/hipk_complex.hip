@@ -722,7 +722,8 @@ zpair_dots_kernel(const cpx<R> *__restrict__ X, int64_t ldX, const cpx<R> *__res
  * coalesced loads, then one lane per row walks its row in LDS and gathers x for NC columns with independent
  * accumulators; y = A x - shift_c x(:,c) when shifts are given.  A tile that is one long row is reduced by the whole
  * workgroup. */
-#define ZTILE_NNZ 2048
+#include "primme_amd_io.h"
+#define ZTILE_NNZ PRIMME_AMD_TILE_NNZ      /* the tiles are the host plan's (csr_tools.c): its limit sizes the LDS arrays */
 struct ZShift { double s[64]; int on; };
 template <typename R>
 __device__ __forceinline__ zacc zfetch_x(const cpx<R> *__restrict__ x, const cpx<R> *__restrict__ xlo, const cpx<R> *__restrict__ xhi,

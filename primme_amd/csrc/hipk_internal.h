@@ -266,6 +266,46 @@ int hipk_z_csr_matvec(hipk_dtype dt, hipStream_t st, const int4 *tileinfo, int n
 int hipk_z_jacobi(hipStream_t st, int num_cu, hipk_dtype dt, int64_t m, const void *diag, const double *shift_host, double min_den, const void *x,
       int64_t ldx, void *y, int64_t ldy, int ncols);
 
+/* ---- the other forms of the CSR operator and its row passes; the hipk_csr object (hipk_csr.hip) owns and calls them ---- */
+struct hipk_pb;
+struct hipk_pat;
+struct hipk_sell;
+extern "C" {
+/* panel-blocked form (hipk_sparse_pb.hip) */
+int hipk_pb_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t n, const int32_t *rp, const int32_t *ci, const void *val, hipk_pb **out);
+int hipk_pb_matvec(const hipk_pb *B, void *hip_stream, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols);
+void hipk_pb_destroy(hipk_pb *B);
+double hipk_pb_bytes(const hipk_pb *B);
+int hipk_pb_panels(const hipk_pb *B);
+/* row-pattern form (hipk_sparse_pat.hip) */
+int hipk_pat_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t row0, const int32_t *rp, const int32_t *ci, const void *val, hipk_pat **out);
+int hipk_pat_build_diag(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int64_t row0, const int32_t *rp, const int32_t *ci, const void *val,
+      const void *diag_dev, hipk_pat **out);
+int hipk_pat_diag(const hipk_pat *B);
+int hipk_pat_matvec(const hipk_pat *B, void *hip_stream, int gx, const void *x, void *y, int64_t halo_lo, int64_t halo_hi, const void *xlo,
+      const void *xhi, const double *norm2, int np2, void *xout, double *partials, const hipk_fin_args *fa);
+void hipk_pat_destroy(hipk_pat *B);
+int hipk_pat_grid(const hipk_pat *B, int num_cu);
+int hipk_pat_grid_kind(const hipk_pat *B, int num_cu, int kind);      /* 0 product, 1 fused tail, 2 Chebyshev step */
+double hipk_pat_bytes(const hipk_pat *B, int fused);
+int hipk_pat_npatterns(const hipk_pat *B);
+int hipk_pat_enabled(void);
+int hipk_pat_cheb_step(const hipk_pat *B, void *hip_stream, int gx, const double cf[4], const void *xr, const void *yk, const void *yp, void *out);
+/* sliced-ELL form (hipk_sparse_sell.hip) */
+int hipk_sell_build(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const int32_t *rp, const int32_t *ci, const void *val, hipk_sell **out);
+void hipk_sell_destroy(hipk_sell *B);
+double hipk_sell_padding(const hipk_sell *B);
+double hipk_sell_bytes(const hipk_sell *B, int ncols);
+int hipk_sell_matvec(const hipk_sell *B, void *hip_stream, int64_t row0, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols,
+      const double *shift_host);
+}
+/* hipk_cheb.hip */
+int hipk_cheb_gershgorin_rows(hipk_ctx *ctx, hipStream_t st, hipk_dtype dt, int64_t nrows, int64_t row0, const int32_t *rowptr,
+      const int32_t *colind, const void *val, double out[2]);
+int hipk_cheb_abs_rowsum_rows(hipk_ctx *ctx, hipStream_t st, hipk_dtype dt, int64_t nrows, const int32_t *rowptr, const void *val, double *out);
+/* d[0..n) = v on the context's stream (hipk_vec.hip) */
+int hipk_fill(hipk_ctx *ctx, hipk_dtype dt, void *d, int64_t n, double v);
+
 #ifdef __HIPCC__
 /* ---- scalar traits: real types now; complex panels use the same kernels ------ */
 template <typename T> struct hipk_num;

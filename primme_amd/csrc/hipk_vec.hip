@@ -792,3 +792,64 @@ extern "C" int hipk_axpy_proj_dot(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int n
       return 0;
    });
 }
+
+/* ============================ fill, Jacobi preconditioner ================================ */
+template <typename T>
+__global__ void __launch_bounds__(HIPK_BLOCK)
+fill_kernel(T *__restrict__ d, int64_t n, double v) {
+   const int64_t stride = (int64_t)gridDim.x * HIPK_BLOCK;
+   for (int64_t i = (int64_t)blockIdx.x * HIPK_BLOCK + threadIdx.x; i < n; i += stride) d[i] = (T)v;
+}
+
+/* d[0..n) = v on the context's stream (library-internal, hipk_internal.h: the diagonal of the stencil operator) */
+int hipk_fill(hipk_ctx *ctx, hipk_dtype dt, void *d, int64_t n, double v) {
+   const int gx = hipk_grid_for_rows(ctx, n, HIPK_BLOCK * 4, 8);
+   DISPATCH_RT(dt, hipLaunchKernelGGL(fill_kernel<T>, dim3(gx), dim3(HIPK_BLOCK), 0, ctx->stream, (T *)d, n, v));
+   HIPK_CHECK(hipGetLastError());
+   return 0;
+}
+
+struct JacShift { double s[64]; };
+template <typename T>
+__global__ void __launch_bounds__(HIPK_BLOCK)
+jacobi_kernel(const T *__restrict__ diag, JacShift sh, double min_den, const T *__restrict__ x, int64_t ldx,
+      T *__restrict__ y, int64_t ldy, int ncols, int64_t m) {
+   const int64_t stride = (int64_t)gridDim.x * HIPK_BLOCK;
+   for (int c = 0; c < ncols; c++) {
+      const double shift = sh.s[c];
+      for (int64_t i = (int64_t)blockIdx.x * HIPK_BLOCK + threadIdx.x; i < m; i += stride) {
+         double d = (double)diag[i] - shift;
+         /* same guard as the reference's test preconditioner: avoid dividing by ~0 */
+         if (!(fabs(d) > min_den)) d = copysign(min_den, d);
+         y[i + (size_t)c * ldy] = (T)((double)x[i + (size_t)c * ldx] / d);
+      }
+   }
+}
+
+extern "C" int hipk_jacobi_apply(void *hip_stream, hipk_dtype dt, int64_t m, const void *diag,
+      const double *shift_host, double min_den, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols) {
+   if (ncols <= 0) return 0;
+   if (!(min_den > 0.0)) min_den = 1e-300;
+   if (ncols > 64) return -1;
+   hipStream_t st = (hipStream_t)hip_stream;
+   hipk_prof_scope ps_(HIPK_PROF_VEC, st, (double)m * (double)hipk_elem_size(dt) * (2.0 * ncols) + (double)m * (double)hipk_elem_size(hipk_real_of(dt)));
+   static int num_cu = 0;                      /* launch geometry only: read the device once */
+   if (num_cu == 0) {
+      int dev = 0, n = 0;
+      if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) num_cu = n;
+      else num_cu = 256;
+   }
+   if (HIPK_IS_Z(dt)) return hipk_z_jacobi(st, num_cu, dt, m, diag, shift_host, min_den, x, ldx, y, ldy, ncols);
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
+   JacShift sh;
+   for (int c = 0; c < ncols; c++) sh.s[c] = shift_host ? shift_host[c] : 0.0;
+   const int64_t need = (m + HIPK_BLOCK * 4 - 1) / (HIPK_BLOCK * 4);
+   const int gx = (int)(need < 1 ? 1 : (need < (int64_t)num_cu * 8 ? need : (int64_t)num_cu * 8));
+   if (dt == HIPK_F64)
+      hipLaunchKernelGGL(jacobi_kernel<double>, dim3(gx), dim3(HIPK_BLOCK), 0, st, (const double *)diag, sh, min_den, (const double *)x, ldx, (double *)y, ldy, ncols, m);
+   else
+      hipLaunchKernelGGL(jacobi_kernel<float>, dim3(gx), dim3(HIPK_BLOCK), 0, st, (const float *)diag, sh, min_den, (const float *)x, ldx, (float *)y, ldy, ncols, m);
+   const hipError_t e = hipGetLastError();
+   if (e != hipSuccess) { fprintf(stderr, "primme_amd: jacobi_kernel launch failed: %s\n", hipGetErrorString(e)); return -1; }
+   return 0;
+}

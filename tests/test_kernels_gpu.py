@@ -11,6 +11,7 @@ import pytest
 from primme_amd import _ffi as F
 from primme_amd import problems
 from kernel_harness import Dev, Host, segs_array, NPDT
+from csr_cases import csr_cases as _csr_cases
 import checkers
 
 pytestmark = pytest.mark.gpu
@@ -331,42 +332,6 @@ def test_qmr_recurrence_kernels(built, dt, m, nx):
         assert np.array_equal(a_[:, m:], b_[:, m:])      # padding rows untouched
 
 
-def _csr_cases():
-    rp, ci, va, n = problems.laplacian_csr((37, 41, 29))
-    yield "lap3d", rp, ci, va, n
-    rp, ci, va, n = problems.laplacian_csr((300, 211))
-    yield "lap2d", rp, ci, va, n
-    # banded, ~17 nonzeros per row inside a +-40 band: every tile's column window is narrow, which is the
-    # case the LDS-windowed block kernel takes (block-diagonal / banded matrices, BASELINE configs[2])
-    rng = np.random.default_rng(8)
-    n = 30011
-    rows = np.repeat(np.arange(n), 17)
-    cols = np.clip(rows + rng.integers(-40, 41, size=rows.size), 0, n - 1)
-    key = np.unique(rows.astype(np.int64) * n + cols)
-    rows, cols = (key // n).astype(np.int64), (key % n).astype(np.int32)
-    rp = np.zeros(n + 1, dtype=np.int64); np.add.at(rp, rows + 1, 1); rp = np.cumsum(rp)
-    yield "banded", rp.astype(np.int32), cols, rng.standard_normal(cols.size), n
-    # ragged: empty rows, one very long row (> LDS tile), random short rows
-    rng = np.random.default_rng(2)
-    n = 5000
-    counts = rng.integers(0, 9, size=n)
-    counts[17] = 0; counts[18] = 0; counts[100] = 4000; counts[n - 1] = 0
-    rp = np.zeros(n + 1, dtype=np.int64); np.cumsum(counts, out=rp[1:])
-    ci = np.concatenate([np.sort(rng.choice(n, size=c, replace=False)) for c in counts]).astype(np.int32)
-    va = rng.standard_normal(len(ci))
-    yield "ragged", rp.astype(np.int32), ci, va, n
-    # all-empty tiles: 300 empty rows first (the first tile has no nonzero), 600 in the middle, 700 at the end (those
-    # tiles' clamped loads land on the padded element behind the last nonzero); and a matrix without any nonzero
-    rng = np.random.default_rng(3)
-    n = 3000
-    counts = rng.integers(1, 7, size=n)
-    counts[:300] = 0; counts[1200:1800] = 0; counts[n - 700:] = 0
-    rp = np.zeros(n + 1, dtype=np.int64); np.cumsum(counts, out=rp[1:])
-    ci = np.concatenate([np.sort(rng.choice(n, size=c, replace=False)) for c in counts if c]).astype(np.int32)
-    yield "empty_tiles", rp.astype(np.int32), ci, rng.standard_normal(len(ci)), n
-    yield "zero_matrix", np.zeros(601, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0), 600
-
-
 @pytest.mark.parametrize("dt", [F.HIPK_F64, F.HIPK_F32])
 @pytest.mark.parametrize("ncols", [1, 3, 8])
 def test_csr_matvec(built, dt, ncols):
@@ -390,6 +355,38 @@ def test_csr_matvec(built, dt, ncols):
         tol = 1e-12 if dt == F.HIPK_F64 else 2e-4
         assert np.max(np.abs(res[0] - res[1])) <= tol * (1 + np.abs(res[1]).max()), name
         assert np.max(np.abs(res[1] - ref)) <= tol * (1 + np.abs(ref).max()), name
+
+
+@pytest.mark.parametrize("dt", [F.HIPK_F64, F.HIPK_F32])
+def test_csr_queries_across_format_switch(built, dt):
+    """The queries about the form in use all read the one routing decision: for the banded matrix (row tiles with the 2-byte
+    index stream; no other form is built for it) format, index bytes and the bytes of the plain and the fused one-column
+    product have their closed forms, and a hipk_set_spmv_format(0 / 1) round trip leaves them as they were."""
+    name, rp, ci, va, n = [c for c in _csr_cases() if c[0] == "banded"][0]
+    npdt = NPDT[dt]
+    es, nnz = np.dtype(npdt).itemsize, len(ci)
+    side = Dev()
+    lib = side.lib
+    lib.hipk_set_spmv_format.argtypes = [C.c_int]
+    lib.hipk_csr_format.argtypes = [C.c_void_p]; lib.hipk_csr_index_bytes.argtypes = [C.c_void_p]
+    lib.hipk_csr_product_bytes.argtypes = [C.c_void_p, C.c_int]; lib.hipk_csr_product_bytes.restype = C.c_double
+    A = C.c_void_p()
+    vv = np.ascontiguousarray(va, dtype=npdt)
+    assert lib.hipk_csr_create(side.ctx, dt, n, n, 0, rp.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                               vv.ctypes.data_as(C.c_void_p), C.byref(A)) == 0
+    read = lambda: (lib.hipk_csr_format(A), lib.hipk_csr_index_bytes(A), lib.hipk_csr_product_bytes(A, 0), lib.hipk_csr_product_bytes(A, 1))
+    want = (0, 2, nnz * (es + 2) + (n + 1) * 4.0 + 2.0 * n * es, nnz * (es + 2) + (n + 1) * 4.0 + 3.0 * n * es)
+    old = lib.hipk_set_spmv_format(1)
+    try:
+        seen = [read()]
+        for fmt in (0, 1):
+            lib.hipk_set_spmv_format(fmt)
+            seen.append(read())
+    finally:
+        lib.hipk_set_spmv_format(old)
+        lib.hipk_csr_destroy(A)
+        side.close()
+    assert seen == [want] * 3, seen
 
 
 def test_inkernel_second_stage_agrees_with_separate_launches(built):
