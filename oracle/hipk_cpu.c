@@ -24,6 +24,8 @@
 #include <string.h>
 #include <time.h>
 #include "primme_amd_kernels.h"
+#include "eigs_internal.h"   /* pa_larnv_uniform11: the host routine checked against LAPACK (tests/test_dense_host.py) */
+#include "hipk_cpu.h"
 
 struct hipk_ctx { int dummy; double t0; };
 
@@ -34,19 +36,6 @@ static double now(void) {
 }
 static size_t esz(hipk_dtype dt) { return dt == HIPK_F64 ? 8 : dt == HIPK_F32 ? 4 : dt == HIPK_C64 ? 16 : 8; }
 #define IS_Z(dt) ((dt) == HIPK_C64 || (dt) == HIPK_C32)
-/* the complex instantiation: oracle/hipk_cpu_complex.c */
-int hipk_z_panel_dots(hipk_dtype dt, int64_t m, const hipk_seg *segs, int nseg, const void *X, int64_t ldX, int nx, double *out, int ldout);
-int hipk_z_panel_project_to(hipk_dtype dt, int64_t m, const hipk_seg *segs, int nseg, const double *coef, int ldcoef, const void *X, int64_t ldX, void *Xout, int64_t ldXout, int nx, double *nrm2);
-int hipk_z_panel_project_mul(hipk_dtype dt, int64_t m, const hipk_seg *segs, int nseg, const double *coef, int ldcoef, const double *M, void *X, int64_t ldX, int nx);
-int hipk_z_ritz_update(hipk_dtype dt, int64_t m, const void *V, const void *W, int64_t ld, int k, const double *h, int ldh, const double *theta, const hipk_job *jobs, int njobs, double *nrm2);
-int hipk_z_scale_cols(hipk_dtype dt, int64_t m, void *X, int64_t ldX, int nx, const double *a);
-int hipk_z_axpy_cols(hipk_dtype dt, int64_t m, const double *a, const void *X, int64_t ldX, void *Y, int64_t ldY, int nx);
-int hipk_z_xpay_cols(hipk_dtype dt, int64_t m, const double *a, const void *X, int64_t ldX, void *Y, int64_t ldY, int nx);
-int hipk_z_col_norms2(hipk_dtype dt, int64_t m, const void *X, int64_t ldX, int nx, double *out);
-int hipk_z_residual_cols(hipk_dtype dt, int64_t m, const void *X, int64_t ldX, void *Wr, int64_t ldW, int nx, const double *theta, double *nrm2);
-int hipk_z_pair_dots(hipk_dtype dt, int64_t m, const void *X, int64_t ldX, const void *Y, int64_t ldY, int nx, double *out);
-int hipk_z_csr_matvec(hipk_dtype dt, int64_t nrows, const int32_t *rp, const int32_t *ci, const void *val, int64_t x0, int64_t xlen, int64_t halo_lo, const void *xlo, int64_t ld_lo, const void *xhi, int64_t ld_hi, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols, const double *shift);
-int hipk_z_jacobi_apply(hipk_dtype dt, int64_t m, const void *diag, const double *shift, double min_den, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols);
 static double ld_(hipk_dtype dt, const void *p, int64_t i) {
    return dt == HIPK_F64 ? ((const double *)p)[i] : (double)((const float *)p)[i];
 }
@@ -86,7 +75,6 @@ int hipk_memset0(hipk_ctx *c, void *d, size_t b) { (void)c; memset(d, 0, b); ret
 int hipk_sync(hipk_ctx *c) { (void)c; return 0; }
 static double *g_mirror_dev, *g_mirror_host; static size_t g_mirror_n;
 int hipk_ctx_set_mirror(hipk_ctx *c, double *d, double *h, size_t n) { (void)c; g_mirror_dev = d; g_mirror_host = h; g_mirror_n = n; return 0; }
-void hipk_cpu_mirror(const double *out, size_t cnt);
 /* the checker's stand-in for the cross-rank second stage of the product's reductions (hipk_finalize_kernel<., XR>): when the stand-in
  * communicator of oracle/hostcheck_glue.c installs this hook, the results of a reduction pass through it (it sums them over the ranks
  * if the pass was armed, hipk_xreduce_arm) before they are mirrored */
@@ -97,7 +85,6 @@ void hipk_cpu_mirror(const double *out, size_t cnt) {   /* keep the zero-copy co
       memmove(g_mirror_host + (out - g_mirror_dev), out, cnt * sizeof(double));
 }
 int hipk_is_device_ptr(const void *p) { return p != NULL; }
-void pa_larnv_uniform11(int64_t iseed[4], int64_t n, double *x);      /* the host routine checked against LAPACK (tests/test_dense_host.py) */
 int hipk_larnv_uniform11(hipk_ctx *ctx, hipk_dtype dt, int64_t iseed[4], int64_t n, void *x) {
    (void)ctx;
    if (n <= 0) return 0;

@@ -14,9 +14,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include "primme_amd_kernels.h"
+#include "hipk_cpu.h"
 
 typedef double _Complex zc;
-void hipk_cpu_mirror(const double *out, size_t cnt);   /* hipk_cpu.c: keeps the zero-copy contract on the host build */
 
 static size_t zesz(hipk_dtype dt) { return dt == HIPK_C64 ? 16 : 8; }
 static zc ldz(hipk_dtype dt, const void *p, int64_t i) {

@@ -8,9 +8,10 @@
 #include "primme_amd_comm.h"
 #include "primme_amd_svds.h"
 #include "primme_amd_io.h"
+#include "eigs_internal.h"   /* the pa_comm_* / hipk_xreduce_* names of the device side that this file stands in for */
+#include "hipk_cpu.h"
 #include <math.h>
 
-typedef void (*hostcheck_allreduce_fn)(double *buf, int count);
 struct primme_amd_comm { hostcheck_allreduce_fn cb; int rank, size; long calls; int xr; long xr_calls; };
 /* comm / xfull: a row slab that references rows of other ranks (halo) gathers the whole vector through the stand-in
  * communicator's all-reduce (every rank contributes its slab to a zero-padded copy) and hands the kernels the two
@@ -91,7 +92,6 @@ void primme_amd_jacobi_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ld
  * on several GPUs -- reductions inside the stream of launches, |t|^2 and t'At in one all-reduce, the fused /
  * speculative restart with reduced overlaps -- in the world_size-2 CPU tests (tests/test_multirank_gloo.py). */
 /* (the stand-in of the cross-rank second stage, below) */
-extern void (*hipk_cpu_xr_hook)(double *out, size_t cnt);
 static primme_amd_comm *g_xr_comm; static int g_xr_armed; static const double *g_xr_lo; static size_t g_xr_count;
 int primme_amd_hostcheck_comm_create(primme_amd_comm **out, hostcheck_allreduce_fn cb, int rank, int size) {
    primme_amd_comm *c = calloc(1, sizeof(*c));

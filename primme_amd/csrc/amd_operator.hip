@@ -7,6 +7,7 @@
 #include "primme_amd.h"
 #include "primme_amd_comm.h"
 #include "comm_internal.h"
+#include "eigs_internal.h"   /* primme_amd_svds_operator_is_local */
 
 struct primme_amd_operator {
    hipk_csr *A;

@@ -18,6 +18,7 @@
  */
 #include "comm_internal.h"
 #include "primme_amd.h"
+#include "eigs_internal.h"   /* the pa_comm_* entry points the host solver calls */
 
 #define NCCL_CHECK(call)                                                              \
    do {                                                                               \

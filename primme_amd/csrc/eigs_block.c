@@ -19,8 +19,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync);
-
 /* number of consecutive linearly independent columns judged from the Gram matrix G (upper) */
 static int rank_estimation(const HS *G, int n0, int n1, int n, int ldG) {
    int i, j;

@@ -31,10 +31,6 @@
 #include "primme_amd_comm.h"
 #include "eigs_internal.h"
 
-int pa_eigs_solve(void *evals_out, void *evecs, void *resNorms_out, primme_params *p, hipk_dtype dt, int out_double);
-/* the complex instantiation of the host solver (eigs_main_z.c and friends, eigs_scalar.h) */
-int pa_eigs_solve_z(void *evals_out, void *evecs, void *resNorms_out, primme_params *p, hipk_dtype dt, int out_double);
-
 /* NATIVE path: complex panels, complex Hermitian projected problem, the reference's zprimme iteration for iteration.
  * Covers the Generalized-Davidson family (GD, GD+k, Olsen variants, LOBPCG-like presets; locking and soft locking;
  * any block size), which includes the default method and BASELINE configs[3], the JDQMR inner-outer iteration

@@ -12,27 +12,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-double pa_problem_norm(int overrideUser, const primme_params *p);
-int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync);
-int pa_ritz_update(pa_solver *s, int basisSize, const hipk_job *jobs, int njobs, double *norms_out,
-      int nslots, int64_t flop_cols);
-int pa_push_coefficients(pa_solver *s, int basisSize, int ldh);
-
-#if !PA_IS_COMPLEX
-/* default convTestFun (reference src/eigs/primme_c.c:555-570) */
-void pa_conv_test_absolute(double *eval, void *evec, double *rNorm, int *isConv,
-      primme_params *p, int *ierr) {
-   (void)eval; (void)evec;
-   /* machine epsilon of the working precision is kept in convtest when we install it */
-   double meps = p->convtest ? *(double *)p->convtest : PA_EPS;
-   *isConv = *rNorm < PA_MAX(p->eps, meps * (p->massMatrixMatvec ? 1 : 2)) * pa_problem_norm(0, p);
-   *ierr = 0;
-}
-
-#else
-void pa_conv_test_absolute(double *eval, void *evec, double *rNorm, int *isConv, primme_params *p, int *ierr);
-#endif
-
 static int call_conv_test(pa_solver *s, double eval, void *evec, double rnorm, int *isconv) {
    primme_params *p = s->p;
    if (p->convTestFun == pa_conv_test_absolute) {
@@ -152,45 +131,10 @@ void pa_map_vecs(const HS *Vp, int mrows, int nV, int ldV, const HS *Wn, int n0,
    free(ip);
 }
 
-#if PA_IS_COMPLEX
-void pa_monitor(pa_solver *s, double *basisEvals, int basisSize, int *basisFlags, int *iblock,
-      int blockSize, double *basisNorms, int numConverged, double *lockedEvals, int numLocked,
-      int *lockedFlags, double *lockedNorms, primme_event event);
-#else
-void pa_monitor(pa_solver *s, double *basisEvals, int basisSize, int *basisFlags, int *iblock,
-      int blockSize, double *basisNorms, int numConverged, double *lockedEvals, int numLocked,
-      int *lockedFlags, double *lockedNorms, primme_event event) {
-   primme_params *p = s->p;
-   p->stats.elapsedTime = pa_wtime() - s->startTime;
-   if (!p->monitorFun) {
-      /* the reference's default report (primme_c.c:602-700), same lines so that logs stay comparable */
-      if (!p->outputFile || p->procID != 0 || p->printLevel < 2) return;
-      const int found = p->locking ? numLocked : numConverged;
-      if (event == primme_event_outer_iteration && p->printLevel >= 3) {
-         for (int i = 0; i < blockSize; i++)
-            fprintf(p->outputFile, "OUT %lld conv %d blk %d MV %lld Sec %E EV %13E |r| %.3E\n",
-                  (long long)p->stats.numOuterIterations, found, i, (long long)p->stats.numMatvecs, p->stats.elapsedTime,
-                  basisEvals[iblock[i]], basisNorms[iblock[i]]);
-      } else if (event == primme_event_converged && ((!p->locking && p->printLevel >= 2) || (p->locking && p->printLevel >= 5))) {
-         fprintf(p->outputFile, "#Converged %d eval[ %d ]= %13E norm %e Mvecs %lld Time %g\n", numConverged, iblock[0],
-               basisEvals[iblock[0]], basisNorms[iblock[0]], (long long)p->stats.numMatvecs, p->stats.elapsedTime);
-      } else if (event == primme_event_locked) {
-         fprintf(p->outputFile, "Lock epair[ %d ]= %13E norm %.4e Mvecs %lld Time %.4e Flag %d\n", numLocked,
-               lockedEvals[numLocked - 1], lockedNorms[numLocked - 1], (long long)p->stats.numMatvecs, p->stats.elapsedTime,
-               lockedFlags[numLocked - 1]);
-      }
-      return;
-   }
-   (void)pa_call_monitor(p, basisEvals, basisSize, basisFlags, iblock, blockSize, basisNorms, numConverged,
-         lockedEvals, numLocked, lockedFlags, lockedNorms, event);
-}
-
+#if !PA_IS_COMPLEX
 /* (the fused block-size-1 paths below are real-arithmetic code: not in the complex objects) */
 /* the library's own operator can run the one-launch tail (scale + A t + t'At) on this solver's panels */
-int pa_svds_can_fuse(const primme_params *primme);
-int pa_svds_apply_scaled(primme_params *primme, hipk_ctx *ctx, const void *t, const double *norm2_dev, void *xout, void *y,
-      double *dot_dev);
-int pa_fuse_tail_eligible(const pa_solver *s) {
+static int pa_fuse_tail_eligible(const pa_solver *s) {
    const primme_params *p = s->p;
    if (s->nT < 1) return 0;                      /* (single columns: the leading dimension does not enter) */
    if (p->matrixMatvec == primme_amd_matvec)
@@ -209,7 +153,7 @@ static int fused_apply(pa_solver *s, const void *t, const double *norm2_dev, voi
 /* The pre-restart convergence check may run through the fused residual kernel and hand its overlaps to the
  * restart: block size 1, GD without preconditioner, Rayleigh-Ritz, in-stream reductions, the library's own
  * operator, and G = W'Q known for all basis vectors but the newest. */
-int pa_restart_stash_eligible(const pa_solver *s, int basisSize, int nLk) {
+static int pa_restart_stash_eligible(const pa_solver *s, int basisSize, int nLk) {
    const primme_params *p = s->p;
    if (!s->fused_restart || !s->fuse_gd || p->maxBlockSize != 1 || !s->rst_y || s->nT < 3) return 0;
    if (!s->wtr_enabled || !s->spec2_enabled || s->Q || s->VtBV || s->phase_timing || (s->parallel && !s->dev_comm)) return 0;
@@ -226,8 +170,6 @@ int pa_restart_stash_eligible(const pa_solver *s, int basisSize, int nLk) {
  * the same pass over V and W that the restart would make anyway; Q'r and W(:,k-1)'Q take one panel product with
  * two right-hand sides.  Returns 1 (done, *norm2 set), 0 (not applicable: the caller runs the fused residual
  * pass on the old basis) or a negative error. */
-int pa_restart_plan(pa_solver *s, int basisSize, const int *flags_in, const int *iev_in, int nblock, int numLocked,
-      int nprevhVecs, const int *map, double *evals, double *resNorms);
 static int try_speculative_restart(pa_solver *s, int basisSize, int nLk, const int *flags, const int *iev, int nblock,
       int numLocked, int nprevhVecs, const int *map, int col, double *evals, double *resNorms, double *norm2) {
    const int K = s->K, ldh = basisSize;
@@ -279,13 +221,6 @@ static int try_speculative_restart(pa_solver *s, int basisSize, int nLk, const i
  * Where t'At of the fused tail goes: a slot at the end of the overlap buffer the pass belongs to (the pre-enqueued
  * iteration must not write where the host is still reading this iteration's). */
 #define PA_ALPHA_OFF(s) ((s)->red_cap - 2)
-
-/* diagnostics of the last solve of this process: iterations enqueued ahead of the host / adopted (include/primme_amd.h) */
-long pa_last_pre[2];
-void primme_amd_prelaunch_stats(long *launched, long *adopted) {
-   if (launched) *launched = pa_last_pre[0];
-   if (adopted) *adopted = pa_last_pre[1];
-}
 
 /* The host-side arithmetic after the one wait of the fused tail: the new column of H from W'r. */
 static void tail_finish(pa_solver *s, int basisSize, int nLk, int nfov, const double *h_fov, double alpha) {
@@ -591,9 +526,6 @@ int pa_speculative_tail(pa_solver *s, int basisSize, int nLk, const char *rsrc, 
 
 /* Put the first unconverged Ritz pairs in the block, computing X, R and the
  * residual norms for them; flag converged pairs on the way. */
-int pa_prepare_vecs(pa_solver *s, int basisSize, int i0, int blockSize, int *arbitraryVecs, double smallestResNorm,
-      const int *flags, int RRForAll);
-
 int pa_prepare_candidates(pa_solver *s, int basisSize, char *X, char *R, int computeXR,
       int *flags, int remainedEvals, double *blockNorms, int blockNormsSize, int maxBlockSize,
       int numLocked, double *evals, double *resNorms, int *iev, int *blockSize,

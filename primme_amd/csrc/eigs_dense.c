@@ -368,16 +368,6 @@ void pa_permute_cols(HS *A, int mrows, int n, int lda, const int *perm) {
    for (int j = 0; j < n; j++) memcpy(A + (size_t)j * lda, tmp + (size_t)j * mrows, (size_t)mrows * sizeof(HS));
    free(tmp);
 }
-#if !PA_IS_COMPLEX      /* type-independent helpers exist once (the real object) */
-void pa_permute_reals(double *A, int mrows, int n, int lda, const int *perm) { pa_permute_cols(A, mrows, n, lda, perm); }
-void pa_permute_ints(int *a, int n, const int *perm) {
-   if (n <= 0) return;
-   int *tmp = (int *)malloc((size_t)n * sizeof(int));
-   for (int j = 0; j < n; j++) tmp[j] = a[perm[j]];
-   memcpy(a, tmp, (size_t)n * sizeof(int));
-   free(tmp);
-}
-#endif
 
 /* R = X' * Hsym * X with Hsym given by its upper triangle (order nh), X nh x nx.
  * (reference src/linalg/auxiliary.c:598-625 compute_submatrix) */
@@ -401,28 +391,6 @@ void pa_submatrix(const HS *X, int nx, int ldx, const HS *H, int nh, int ldh, HS
       }
    free(t);
 }
-
-#if !PA_IS_COMPLEX
-/* LAPACK xLARNV(idist = 2) stream, restated: 48-bit multiplicative congruential
- * generator x <- a*x mod 2^48, a = 33952834046453, uniform(-1,1) = 2*x/2^48 - 1.
- * iseed holds the state as four base-4096 digits (updated on exit).  Verified
- * bit-for-bit against the LAPACK in this image (tests/test_dense_host.py).
- * The reference calls this through Num_larnv_Sprimme (blaslapack.c:938-988). */
-void pa_larnv_uniform11(int64_t iseed[4], int64_t n, double *x) {
-   const uint64_t A = 33952834046453ULL, MASK = (1ULL << 48) - 1;
-   uint64_t s = ((((uint64_t)iseed[0] * 4096 + (uint64_t)iseed[1]) * 4096 + (uint64_t)iseed[2]) * 4096 +
-                 (uint64_t)iseed[3]) & MASK;
-   for (int64_t i = 0; i < n; i++) {
-      s = (s * A) & MASK;
-      x[i] = 2.0 * ((double)s / 281474976710656.0) - 1.0;
-   }
-   iseed[0] = (int64_t)((s >> 36) & 4095);
-   iseed[1] = (int64_t)((s >> 24) & 4095);
-   iseed[2] = (int64_t)((s >> 12) & 4095);
-   iseed[3] = (int64_t)(s & 4095);
-}
-
-#endif   /* !PA_IS_COMPLEX */
 
 /* ---- singular value decomposition A = U diag(S) V' of a small square matrix ------------------
  * One-sided Jacobi (Hestenes): columns of W = A V are rotated until mutually orthogonal; S are

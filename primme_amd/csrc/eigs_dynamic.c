@@ -19,8 +19,6 @@
 #include "eigs_solver.h"
 #include <math.h>
 
-int pa_reduce_host(pa_solver *s, double *buf, int count);
-
 void pa_dyn_init(pa_cost_model *c, const primme_params *p) {
    c->t_mv_pr = c->t_mv = c->t_pr = 0.0;
    c->t_qmr = c->t_qmr_mv_pr = 0.0;

@@ -22,12 +22,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync);
-int pa_solve_H_RR(pa_solver *s, const HS *H, int ldH, const HS *VtBV, int ldVtBV,
-      HS *hVecs, int ldhVecs, double *hVals, int n, int numConverged);
-int pa_ortho_local_vec(HS *x, int n, const HS *Q, int ldQ, int nQ, const HS *G,
-      int ldG, double *R, int64_t iseed[4]);
-
 /* CGS + Daniel reorthogonalisation of Q(:, b1..b2) against Q(:, 0..i-1), coefficients into R
  * (reference ortho.c:123-360 with R != NULL).  Stops at the first column that vanishes. */
 static int ortho_Q(pa_solver *s, int b1, int b2, int *nQ_out) {
@@ -191,7 +185,6 @@ int pa_restart_harmonic(pa_solver *s, int ldh, int restartSize, int basisSize, i
  *                                                          singular values ("arbitrary vectors")
  *   pa_restart_refined   <- restart.c:1837-2160          Q, R after V <- V h without re-factorising
  * The QR factorisation (A - tau I) V = Q R is the one of the harmonic path (pa_update_Q). */
-int pa_svd(const HS *A, int ldA, int n, HS *U, int ldU, double *S, HS *V, int ldV);
 
 int pa_solve_H_ref(pa_solver *s, int k, double *hVals_out) {
    primme_params *p = s->p;

@@ -30,15 +30,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-double pa_problem_norm(int overrideUser, const primme_params *p);
-int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync);
-int pa_matvec(pa_solver *s, char *Vp, int64_t ldV, char *Wp, int64_t ldW, int c0, int nc);
-int pa_precond(pa_solver *s, char *X, int64_t ldX, char *Y, int64_t ldY, int nc);
-void pa_conv_test_absolute(double *eval, void *evec, double *rNorm, int *isConv, primme_params *p, int *ierr);
-void pa_monitor(pa_solver *s, double *basisEvals, int basisSize, int *basisFlags, int *iblock,
-      int blockSize, double *basisNorms, int numConverged, double *lockedEvals, int numLocked,
-      int *lockedFlags, double *lockedNorms, primme_event event);
-
 /* The QMR recurrences are REAL for complex data too (the reference takes real parts: Num_dist_dots_real,
  * inner_solve.c:283-420, and real axpy factors): on a complex panel those steps are the real kernels on the panel seen as
  * 2m reals (Re(x^H y) = the real inner product of the two 2m-vectors).  Only the operator and the projectors work with
@@ -391,16 +382,6 @@ static int apply_projected_preconditioner(pa_solver *s, char *v, int64_t ldv, co
    return 0;
 }
 
-#if !PA_IS_COMPLEX
-/* diagnostics of this process (include/primme_amd.h): inner QMR steps taken / taken with one host synchronisation since the last call */
-static long g_qmr_steps[2];
-void primme_amd_qmr_step_stats(long *steps, long *one_synchronisation) {
-   if (steps) *steps = g_qmr_steps[0];
-   if (one_synchronisation) *one_synchronisation = g_qmr_steps[1];
-   g_qmr_steps[0] = g_qmr_steps[1] = 0;
-}
-#endif
-
 /* Block QMR.  x, r: the block's Ritz vectors and residuals (V / W slots at basisSize);
  * sol receives the corrections.  eval[i], shift[i], rnorm[i] per block vector. */
 static int inner_solve(pa_solver *s, int blockSize, char *x, char *r, const double *rnorm, jd_proj *P,
@@ -499,11 +480,11 @@ static int inner_solve(pa_solver *s, int blockSize, char *x, char *r, const doub
                           !(s->parallel && !s->dev_comm) && 3 * 64 + 3 * 8 < s->red_cap;
       double gg_all[8], rho_all[8], dot_all[8];
 #if !PA_IS_COMPLEX
-      g_qmr_steps[0]++;
+      pa_qmr_steps[0]++;
 #endif
       if (onewait) {
 #if !PA_IS_COMPLEX
-         g_qmr_steps[1]++;
+         pa_qmr_steps[1]++;
          double rp[8], tp[8], thp[8], jsh[8];
          double *d_tri = s->d_red, *d_ggr = s->d_red + 3 * 64, *d_dot = s->d_red + 3 * 64 + 16;
          for (i = 0; i < blockSize; i++) {

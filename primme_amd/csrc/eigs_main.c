@@ -20,45 +20,8 @@
 #include <string.h>
 #include <limits.h>
 
-double pa_problem_norm(int overrideUser, const primme_params *p);
-int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync);
-int pa_refresh_wtq(pa_solver *s, int basisSize, int nLk);
-int pa_block_first_reorder(pa_solver *s, int basisSize, int *flags, const int *iev, int blockSize, int numConverged, int numLocked);
-int pa_matvec(pa_solver *s, char *Vp, int64_t ldV, char *Wp, int64_t ldW, int c0, int nc);
-int pa_precond(pa_solver *s, char *X, int64_t ldX, char *Y, int64_t ldY, int nc);
-int pa_random_col(pa_solver *s, char *col);
-int pa_ortho_cgs(pa_solver *s, char *Vp, int64_t ldV, int b1, int b2, char *locked,
-      int64_t ldLocked, int numLocked, HS *RLocked, int ldRLocked, int *b2_out);
-int pa_update_projection(pa_solver *s, int numCols, int blockSize);
-int pa_solve_H(pa_solver *s, int basisSize, int numLocked, int numConverged);
-int pa_push_coefficients(pa_solver *s, int basisSize, int ldh);
-int pa_ritz_update(pa_solver *s, int basisSize, const hipk_job *jobs, int njobs, double *norms_out,
-      int nslots, int64_t flop_cols);
-void pa_conv_test_absolute(double *eval, void *evec, double *rNorm, int *isConv,
-      primme_params *p, int *ierr);
-int pa_check_convergence(pa_solver *s, char *X, int64_t ldX, int givenX, char *R, int64_t ldR,
-      int givenR, int numLocked, int left, int right, int *flags, double *blockNorms,
-      const double *hVals, int *reset, int practConvCheck);
-void pa_map_vecs(const HS *Vp, int mrows, int nV, int ldV, const HS *Wn, int n0, int n,
-      int ldW, int *pm);
-void pa_monitor(pa_solver *s, double *basisEvals, int basisSize, int *basisFlags, int *iblock,
-      int blockSize, double *basisNorms, int numConverged, double *lockedEvals, int numLocked,
-      int *lockedFlags, double *lockedNorms, primme_event event);
-int pa_prepare_candidates(pa_solver *s, int basisSize, char *X, char *R, int computeXR,
-      int *flags, int remainedEvals, double *blockNorms, int blockNormsSize, int maxBlockSize,
-      int numLocked, double *evals, double *resNorms, int *iev, int *blockSize,
-      int *recentlyConverged, double *smallestResNorm, int numConverged, double *basisNorms,
-      int *reset, int nprevhVecs, int practConvChecking, int *map);
-int pa_restart(pa_solver *s, int basisSize, int *flags, int *iev, int *ievSize, double *blockNorms,
-      int *evecsPerm, double *evals, double *resNorms, int *numConverged, int *numLocked,
-      int *lockedFlags, int nprevhVecs, int numGuesses, int *restartSizeOutput,
-      int *restartsSinceReset);
-
 /* ---- block orthogonalisation dispatcher (reference ortho.c:429-439, :522-530):
  *      implicit_I -> vector-by-vector CGS. ----------------------------------------- */
-int pa_ortho_block_gram(pa_solver *s, char *Vp, int64_t ldV, int b1, int b2, char *locked,
-      int64_t ldLocked, int numLocked, HS *RLocked, int ldRLocked, int maxRank, int *b2_out);
-
 static int ortho_block(pa_solver *s, char *Vp, int64_t ldV, int b1, int b2, char *locked,
       int64_t ldLocked, int numLocked, HS *RLocked, int ldRLocked, int *b2_out) {
    if (b2 < b1) { *b2_out = b2 + 1; return 0; }
@@ -151,21 +114,6 @@ static void merge_sort(const double *lockedEvals, int numLocked, const double *r
 
 /* GD correction: t = K^-1 (r - eps x) (approximate Olsen when RightX) or K^-1 r;
  * without a preconditioner a device copy.  Writes the correction over X. */
-void pa_dyn_init(pa_cost_model *c, const primme_params *p);
-int pa_dyn_observe(pa_cost_model *c, primme_params *p, double now, int recentConv, int atRestart,
-      int numConverged, double currentResNorm);
-int pa_dyn_leave_gd(pa_solver *s, pa_cost_model *c);
-int pa_dyn_leave_jdqmr(pa_solver *s, pa_cost_model *c);
-void pa_dyn_recommend(const pa_cost_model *c, primme_params *p);
-int pa_update_Q(pa_solver *s, double tau, int col0, int bs, int *nQ);
-int pa_update_QtV(pa_solver *s, int col0, int bs);
-int pa_prepare_vecs(pa_solver *s, int basisSize, int i0, int blockSize, int *arbitraryVecs, double smallestResNorm,
-      const int *flags, int RRForAll);
-int pa_evecs_hat_init(pa_solver *s);
-int pa_evecs_hat_update(pa_solver *s, int *numConvergedStored, int numConverged);
-int pa_correction_jdqmr(pa_solver *s, int basisSize, int blockSize, const double *blockNorms, const int *iev,
-      double *shifts, int numLocked, int numConvergedStored, int *touch);
-
 static int solve_correction_gd(pa_solver *s, const double *lockedEvals, int numLocked, int *flags,
       int basisSize, double *blockNorms, int *iev, int blockSize, int numConvergedStored, int *touch) {
    primme_params *p = s->p;
@@ -828,17 +776,11 @@ static void free_solver(pa_solver *s) {
    free(s);
 }
 
-extern void primme_amd_global_sum(void *, void *, int *, struct primme_params *, int *);
-
-int pa_svds_conv_test_is_vector_free(const primme_params *p);
-
-static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params *p, hipk_dtype dt, int out_double) {
-   const double t0 = pa_wtime();
-   if (!p) return -4;
+/* ---- parameter normalisation: defaults, seeds, operand types of the callbacks, the default convergence test.
+ *      Returns 1 when the call only asks for the defaults (no array given): nothing to solve. ---- */
+static int normalise_params(primme_params *p, hipk_dtype dt, double mach_eps, const void *evals_out, const void *evecs,
+      const void *resNorms_out) {
    const int work_is_float = (dt == HIPK_F32 || dt == HIPK_C32);
-   const int real_out_is_float = work_is_float && !out_double;
-   const double mach_eps = work_is_float ? 1.1920928955078125e-07 : PA_EPS;
-
    if (p->numProcs <= 1 && evals_out && evecs && resNorms_out) { p->nLocal = p->n; p->procID = 0; }
    primme_set_defaults(p);
    if (p->orth == primme_orth_default)
@@ -847,7 +789,7 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
     * orth = implicit_I; same subspaces, another orthonormalisation of them) */
    if (p->massMatrixMatvec) p->orth = primme_orth_explicit_I;
    if (p->ldOPs == -1) p->ldOPs = p->nLocal;
-   if (!evals_out && !evecs && !resNorms_out) return 0;
+   if (!evals_out && !evecs && !resNorms_out) return 1;
    if (p->iseed[0] < 0 || p->iseed[0] > 4095) p->iseed[0] = p->procID % 4096;
    if (p->iseed[1] < 0 || p->iseed[1] > 4095) p->iseed[1] = (int)(p->procID / 4096 + 1) % 4096;
    if (p->iseed[2] < 0 || p->iseed[2] > 4095) p->iseed[2] = (int)((p->procID / 4096) / 4096 + 2) % 4096;
@@ -866,13 +808,14 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
    }
    if (!p->convTestFun) {
       p->convTestFun = pa_conv_test_absolute;
-      p->convTestFun_type = (dt == HIPK_F32 || dt == HIPK_C32) ? primme_op_float : primme_op_double;
+      p->convTestFun_type = work_is_float ? primme_op_float : primme_op_double;
       if (p->eps == 0.0) p->eps = mach_eps * 1e4;
    }
-   int rc = pa_check_input(evals_out, evecs, resNorms_out, p, mach_eps);
-   if (rc) return rc;
+   return 0;
+}
 
-   /* what this build of the path covers; anything else must fail loudly */
+/* ---- what this build of the path covers; anything else must fail loudly (PRIMME_FUNCTION_UNAVAILABLE) ---- */
+static int check_coverage(primme_params *p, hipk_dtype dt) {
 #if PA_IS_COMPLEX
    if (dt != HIPK_C64 && dt != HIPK_C32) return PRIMME_FUNCTION_UNAVAILABLE;
    /* the complex objects carry the three extractions with the Generalized-Davidson family, the JDQMR inner solver and the
@@ -890,7 +833,8 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
    /* mass matrix (round 6): real and complex Hermitian panels, Rayleigh-Ritz (check_input: -39 otherwise, like the reference), the
     * Generalized-Davidson family, the JDQMR inner solver (projectors on B Q and B x, eigs_jd.c) and the dynamic switch between them.
     * PRIMME_AMD_MASS_NO_DYNAMIC=1 keeps a PRIMME_DYNAMIC run in its GD+k mode (what the reference's own switch does when it
-    * leaves JDQMR: maxInnerIterations = 0, state -2 on return, main_iter.c:2330-2345, :1221-1228): an A/B knob. */
+    * leaves JDQMR: maxInnerIterations = 0, state -2 on return, main_iter.c:2330-2345, :1221-1228): an A/B knob, applied here,
+    * between the gates, so that a call turned away leaves *p as it always did. */
    if (p->massMatrixMatvec && p->dynamicMethodSwitch > 0 && getenv("PRIMME_AMD_MASS_NO_DYNAMIC") != NULL) {
       p->dynamicMethodSwitch = -2;
       p->correctionParams.maxInnerIterations = 0;
@@ -911,17 +855,42 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
          fprintf(p->outputFile, "primme_amd: maxBasisSize > %d is not on the device path\n", max_basis);
       return PRIMME_FUNCTION_UNAVAILABLE;
    }
+   return 0;
+}
 
+/* ---- the solver's state: sizes, the knobs, the device context and every allocation of the solve.  *out is set as soon
+ *      as there is something to free: on an error the caller hands it to free_solver like a complete one. ---- */
+static int solver_create(pa_solver **out, primme_params *p, hipk_dtype dt, double mach_eps, void *evecs, double t0) {
+   const int refined = (p->projectionParams.projection == primme_proj_refined);
+   const int harmonic = (p->projectionParams.projection == primme_proj_harmonic) || refined;
    pa_solver *s = (pa_solver *)calloc(1, sizeof(pa_solver));
    if (!s) return PRIMME_MALLOC_FAILURE;
+   *out = s;
+
+   /* the knobs, each read once per solve.  PRIMME_AMD_NO_LDPAD=1 keeps ldOPs (below) */
+   const int no_ldpad = getenv("PRIMME_AMD_NO_LDPAD") != NULL;
+   /* PRIMME_AMD_FORCE_COMM: run the cross-rank reduction path with a one-rank communicator, which is
+    * how the RCCL calls are exercised on a single-GPU box (tests/test_comm_gpu.py) */
+   const int force_comm = getenv("PRIMME_AMD_FORCE_COMM") != NULL;
+   const int ref_soft_locking = getenv("PRIMME_AMD_JDQMR_REF_SOFT_LOCKING") != NULL;      /* (eigs_solver.h: ref_soft_alias) */
+   const int no_spec_restart = getenv("PRIMME_AMD_NO_SPEC_RESTART") != NULL;               /* no alternate panels V2 / W2 */
+   s->spec2_enabled = getenv("PRIMME_AMD_NO_SPEC2") == NULL;
+   /* projection column from W'r of the fused residual pass (DESIGN.md §4d): default; PRIMME_AMD_NO_WTR
+    * switches back to the separate pass over V (measurement knob) */
+   s->wtr_enabled = getenv("PRIMME_AMD_NO_WTR") == NULL;
+   s->device_rr = getenv("PRIMME_AMD_DEVICE_RR") != NULL;
+   s->fused_restart = getenv("PRIMME_AMD_NO_FUSED_RESTART") == NULL;
+   s->pre_enabled = getenv("PRIMME_AMD_NO_PRELAUNCH") == NULL;
+   s->pre_quiet_fin = getenv("PRIMME_AMD_LOUD_FIN") == NULL;
+
    s->p = p; s->dt = dt; s->es = (dt == HIPK_F64) ? 8 : (dt == HIPK_F32) ? 4 : (dt == HIPK_C64) ? 16 : 8; s->mach_eps = mach_eps;
    s->m = p->nLocal; s->ld = p->ldOPs; s->K = p->maxBasisSize;
    /* Columns of V, W and the scratch panels on 128-byte boundaries when nobody outside the library sees their leading
     * dimension (its own operator and preconditioner, ldOPs left at nLocal): a wave's 1 KB of a column is then 8 cache
     * lines instead of 9 (the fused residual kernel: 132 -> 121 us at k = 15, m = 2 000 250, whose columns are only
-    * 16-byte aligned).  PRIMME_AMD_NO_LDPAD=1 keeps ldOPs. */
+    * 16-byte aligned). */
    if (p->matrixMatvec == primme_amd_matvec && (!p->applyPreconditioner || p->applyPreconditioner == primme_amd_jacobi_precond) &&
-         p->ldOPs == p->nLocal && p->nLocal > 256 && getenv("PRIMME_AMD_NO_LDPAD") == NULL) {
+         p->ldOPs == p->nLocal && p->nLocal > 256 && !no_ldpad) {
       const int64_t q = (int64_t)(128 / s->es);
       s->ld = (p->nLocal + q - 1) / q * q;
    }
@@ -929,14 +898,7 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
    s->startTime = t0;
    /* the dynamic method's cost model needs device time, not launch time */
    s->phase_timing = p->profile != NULL || p->dynamicMethodSwitch > 0;
-   /* PRIMME_AMD_FORCE_COMM: run the cross-rank reduction path with a one-rank communicator, which is
-    * how the RCCL calls are exercised on a single-GPU box (tests/test_comm_gpu.py) */
-   s->spec2_enabled = getenv("PRIMME_AMD_NO_SPEC2") == NULL;
-   /* projection column from W'r of the fused residual pass (DESIGN.md §4d): default; PRIMME_AMD_NO_WTR
-    * switches back to the separate pass over V (measurement knob, read once per solve) */
-   s->wtr_enabled = getenv("PRIMME_AMD_NO_WTR") == NULL;
-   s->device_rr = getenv("PRIMME_AMD_DEVICE_RR") != NULL;
-   s->parallel = ((p->numProcs > 1 || getenv("PRIMME_AMD_FORCE_COMM")) && p->globalSumReal != NULL);
+   s->parallel = ((p->numProcs > 1 || force_comm) && p->globalSumReal != NULL);
    s->dev_comm = (s->parallel && p->globalSumReal == primme_amd_global_sum);
    s->coef_valid_k = -1;
    s->fuse_gd = !PA_IS_COMPLEX && (p->correctionParams.maxInnerIterations == 0 && p->dynamicMethodSwitch <= 0 && !p->correctionParams.precondition &&
@@ -945,15 +907,11 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
    s->maxRank = p->numOrthoConst + (p->locking ? p->numEvals : 0) + p->maxBasisSize;
    s->B = p->massMatrixMatvec != NULL;
    if (s->B) s->fuse_gd = 0;
-   s->ref_soft_alias = s->B && !p->locking && getenv("PRIMME_AMD_JDQMR_REF_SOFT_LOCKING") != NULL;
-   if (hipk_ctx_create(&s->ctx, p->queue)) { free(s); return PRIMME_UNEXPECTED_FAILURE; }
+   s->ref_soft_alias = s->B && !p->locking && ref_soft_locking;
+   s->wtq_rows = -1;
+   if (hipk_ctx_create(&s->ctx, p->queue)) return PRIMME_UNEXPECTED_FAILURE;
    /* peer-to-peer transport: the second stage of a reduction may exchange with the other ranks itself */
    if (s->dev_comm) (void)pa_comm_attach_ctx(p->commInfo, s->ctx);
-   /* callbacks find the solver's stream in primme->queue (reference: the queue/handle
-    * field carries the device queue, examples/ex_eigs_dhipblas.c:177-179) */
-   void *user_queue = p->queue;
-   void *own_stream = hipk_ctx_stream(s->ctx);
-   if (!p->queue) p->queue = &own_stream;
 
    const int K = s->K, nev = p->numEvals, b = p->maxBlockSize;
    s->nT = K + 2 * b + 2;
@@ -971,9 +929,9 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
       s->Mq = (HS *)calloc((size_t)maxEvecs * maxEvecs + 1, sizeof(HS));
       s->Mlu = (HS *)calloc((size_t)maxEvecs * maxEvecs + 1, sizeof(HS));
       s->Mpiv = (int *)calloc((size_t)maxEvecs + 1, sizeof(int));
-      if (!s->Mq || !s->Mlu || !s->Mpiv) { free_solver(s); p->queue = user_queue; return PRIMME_MALLOC_FAILURE; }
+      if (!s->Mq || !s->Mlu || !s->Mpiv) return PRIMME_MALLOC_FAILURE;
    }
-   rc = hipk_malloc(s->ctx, colBytes * K, (void **)&s->V) || hipk_malloc(s->ctx, colBytes * K, (void **)&s->W) ||
+   int rc = hipk_malloc(s->ctx, colBytes * K, (void **)&s->V) || hipk_malloc(s->ctx, colBytes * K, (void **)&s->W) ||
         hipk_malloc(s->ctx, colBytes * s->nT, (void **)&s->T) ||
         ((p->correctionParams.maxInnerIterations != 0 || p->dynamicMethodSwitch > 0) && hipk_malloc(s->ctx, colBytes * (s->B ? 8 : 6) * b, (void **)&s->Jw)) ||
         (s->B && (p->correctionParams.maxInnerIterations != 0 || p->dynamicMethodSwitch > 0) &&
@@ -995,8 +953,6 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
    s->rst_ov = (double *)calloc(4 * (size_t)HIPK_WTR_MAX_K + 4, 8);
    s->rst_c = (double *)calloc(4 * (size_t)HIPK_WTR_MAX_K + 4, 8);
    s->rst_grow = (double *)calloc((size_t)HIPK_WTR_MAX_K + 1, 8);
-   s->fused_restart = getenv("PRIMME_AMD_NO_FUSED_RESTART") == NULL;
-   s->wtq_rows = -1;
    if (harmonic) {
       s->R = (HS *)calloc((size_t)K * K + 1, sizeof(HS));
       s->hU = (HS *)calloc((size_t)K * K + 1, sizeof(HS));
@@ -1004,7 +960,7 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
          s->refined = 1;
          s->hSVals = (double *)calloc((size_t)K + 1, 8); s->hVecsRot = (HS *)calloc((size_t)K * K + 1, sizeof(HS));
       } else s->QtV = (HS *)calloc((size_t)K * K + 1, sizeof(HS));
-      if (!s->R || !s->hU || (refined ? (!s->hSVals || !s->hVecsRot) : !s->QtV)) { free_solver(s); p->queue = user_queue; return PRIMME_MALLOC_FAILURE; }
+      if (!s->R || !s->hU || (refined ? (!s->hSVals || !s->hVecsRot) : !s->QtV)) return PRIMME_MALLOC_FAILURE;
    }
    s->flags = (int *)calloc((size_t)K, sizeof(int)); s->map = (int *)calloc((size_t)K, sizeof(int));
    s->iev = (int *)calloc((size_t)K + b, sizeof(int)); s->perm = (int *)calloc((size_t)nev + 1, sizeof(int));
@@ -1023,10 +979,8 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
       s->d_hnext = s->d_red + 3 * (size_t)s->red_cap; s->h_hnext = s->h_red + 3 * (size_t)s->red_cap;
       rc = hipk_memset0(s->ctx, s->d_red, ((size_t)s->red_cap * 3 + 64) * 8);
    }
-   s->pre_enabled = getenv("PRIMME_AMD_NO_PRELAUNCH") == NULL;
-   s->pre_quiet_fin = getenv("PRIMME_AMD_LOUD_FIN") == NULL;
    if (!rc && s->fused_restart && s->fuse_gd && b == 1 && !harmonic && K <= 32 && s->nT >= 4 &&
-         s->red_cap >= 64 + 2 * HIPK_WTR_MAX_K && getenv("PRIMME_AMD_NO_SPEC_RESTART") == NULL) {
+         s->red_cap >= 64 + 2 * HIPK_WTR_MAX_K && !no_spec_restart) {
       /* alternate panels of the speculative restart (eigs_solver.h); without them the restart runs in place */
       if (hipk_malloc(s->ctx, colBytes * K, (void **)&s->V2) || hipk_malloc(s->ctx, colBytes * K, (void **)&s->W2) ||
             /* coefficient block and Ritz values of the planned restart in ONE buffer (values behind the K x K block), on the device
@@ -1041,16 +995,20 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
       s->h_theta2 = s->h_coef2 ? s->h_coef2 + (size_t)K * K : NULL;
    }
    if (rc || !s->H || !s->hVecs || !s->prevhVecs || !s->hVals || !s->prevRitzVals || !s->blockNorms ||
-         !s->basisNorms || !s->flags || !s->map || !s->iev || !s->perm || !s->lockedFlags) {
-      free_solver(s);
-      p->queue = user_queue;
+         !s->basisNorms || !s->flags || !s->map || !s->iev || !s->perm || !s->lockedFlags)
       return PRIMME_MALLOC_FAILURE;
-   }
+   return 0;
+}
 
+/* ---- run the iteration, narrow the outputs to the caller's type, publish the statistics of the solve ---- */
+static int solver_run(pa_solver *s, void *evals_out, void *resNorms_out, int real_out_is_float) {
+   primme_params *p = s->p;
+   const int nev = p->numEvals;
    /* evals / resNorms are kept in double inside and narrowed on exit */
    double *evals = (double *)calloc((size_t)nev + 1, 8), *resNorms = (double *)calloc((size_t)nev + 1, 8);
+   if (!evals || !resNorms) { free(evals); free(resNorms); return PRIMME_MALLOC_FAILURE; }
    int ret = 0, numRet = 0;
-   rc = main_iter(s, evals, resNorms, &ret, &numRet);
+   int rc = main_iter(s, evals, resNorms, &ret, &numRet);
    if (!rc) {
       for (int i = 0; i < numRet; i++) {
          if (real_out_is_float) { ((float *)evals_out)[i] = (float)evals[i]; ((float *)resNorms_out)[i] = (float)resNorms[i]; }
@@ -1064,10 +1022,36 @@ static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params
    if (getenv("PRIMME_AMD_PRELAUNCH_STATS"))
       fprintf(stderr, "primme_amd: iterations enqueued ahead of the host: %ld launched, %ld adopted (of %lld outer iterations)\n", s->pre_launched,
             s->pre_adopted, (long long)p->stats.numOuterIterations);
-   if (p->convTestFun == pa_conv_test_absolute) { /* leave the struct as the reference does: default installed */ }
-   free_solver(s);
+   return rc;
+}
+
+static int solve(void *evals_out, void *evecs, void *resNorms_out, primme_params *p, hipk_dtype dt, int out_double) {
+   const double t0 = pa_wtime();
+   if (!p) return -4;
+   const int work_is_float = (dt == HIPK_F32 || dt == HIPK_C32);
+   const double mach_eps = work_is_float ? 1.1920928955078125e-07 : PA_EPS;
+
+   if (normalise_params(p, dt, mach_eps, evals_out, evecs, resNorms_out)) return 0;
+   int rc = pa_check_input(evals_out, evecs, resNorms_out, p, mach_eps);
+   if (rc) return rc;
+   rc = check_coverage(p, dt);
+   if (rc) return rc;
+
+   pa_solver *s = NULL;
+   void *const user_queue = p->queue;
+   void *own_stream = NULL;
+   rc = solver_create(&s, p, dt, mach_eps, evecs, t0);
+   const int created = (rc == 0);
+   if (created) {
+      /* callbacks find the solver's stream in primme->queue (reference: the queue/handle
+       * field carries the device queue, examples/ex_eigs_dhipblas.c:177-179) */
+      own_stream = hipk_ctx_stream(s->ctx);
+      if (!p->queue) p->queue = &own_stream;
+      rc = solver_run(s, evals_out, resNorms_out, work_is_float && !out_double);
+   }
+   free_solver(s);      /* (a solver that solver_create left incomplete as well) */
    p->queue = user_queue;
-   p->stats.elapsedTime = pa_wtime() - t0;
+   if (created) p->stats.elapsedTime = pa_wtime() - t0;
    return rc;
 }
 

@@ -14,180 +14,6 @@
 #include <string.h>
 #include <time.h>
 
-#if !PA_IS_COMPLEX      /* type-independent pieces exist once (the real objects) */
-double pa_wtime(void) {
-   struct timespec ts;
-   clock_gettime(CLOCK_MONOTONIC, &ts);
-   return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
-/* ---- problem norm / machine epsilons (reference auxiliary_eigs.c:498-591) ------ */
-double pa_problem_norm(int overrideUser, const primme_params *p) {
-   if (p->massMatrixMatvec) {      /* an estimate of |B^-1 A| (auxiliary_eigs.c:567-591) */
-      const double user = (p->aNorm > 0.0 && p->invBNorm > 0.0) ? p->aNorm * p->invBNorm : 0.0;
-      if (!overrideUser) return user > 0.0 ? user : p->stats.estimateLargestSVal;
-      return PA_MAX(user, p->stats.estimateLargestSVal);
-   }
-   if (!overrideUser) return p->aNorm > 0.0 ? p->aNorm : p->stats.estimateLargestSVal;
-   return PA_MAX(p->aNorm > 0.0 ? p->aNorm : 0.0, p->stats.estimateLargestSVal);
-}
-
-/* ---- reductions -----------------------------------------------------------------
- * d_buf (device) holds `count` local partial sums.  On return s->h_red[0..count)
- * holds the global sums; if keep_dev, d_buf holds them as well (the next kernel
- * uses them as coefficients).  Restates globalSum_Tprimme (reference
- * auxiliary_eigs.c:391-427) for device-resident partials.
- * When defer_sync is set and no host callback is involved, the device->host copy
- * is only enqueued; the caller must hipk_sync before reading h_red. */
-int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync) {
-   primme_params *p = s->p;
-   if (count <= 0) return 0;
-   /* d_buf lies in [d_red, d_red + 2*red_cap): the second half holds the fused kernel's overlaps */
-   if (d_buf < s->d_red || (size_t)(d_buf - s->d_red) + (size_t)count > 3 * (size_t)s->red_cap + 64) return PRIMME_UNEXPECTED_FAILURE;
-   const int parallel = s->parallel;
-   double t0 = parallel ? pa_wtime() : 0.0;
-   if (parallel && s->dev_comm) {
-      if (hipk_xreduce_covered(s->ctx, d_buf, count)) {
-         /* the producing launch's second stage exchanged its sums with the other ranks itself (peer-to-peer
-          * transport, hipk_xreduce_arm): d_buf and the pinned mirror already hold the global sums */
-         if (!defer_sync) CHK(hipk_wait_results(s->ctx));
-      } else {
-      /* peer-to-peer transport: reduction, mirror and completion flag are one launch */
-      int rcp = pa_comm_allreduce_publish(p->commInfo, s->ctx, d_buf, count);
-      if (rcp < 0) return PRIMME_PARALLEL_FAILURE;
-      if (rcp == 0) {
-         if (!defer_sync) CHK(hipk_wait_results(s->ctx));
-      } else {
-      CHK(pa_comm_allreduce_device(p->commInfo, d_buf, count, hipk_ctx_stream(s->ctx)));
-      /* the global sums reach the pinned mirror through a one-block launch that also publishes the completion flag
-       * (the wait is then a spin on pinned memory, as on one rank); fallback: copy + stream synchronisation */
-      static int no_publish = -1;      /* PRIMME_AMD_NO_PUBLISH=1: measurement knob, read once */
-      if (no_publish < 0) no_publish = getenv("PRIMME_AMD_NO_PUBLISH") != NULL;
-      rcp = no_publish ? 1 : hipk_publish_results(s->ctx, d_buf, count);
-      if (rcp < 0) return PRIMME_UNEXPECTED_FAILURE;
-      if (rcp == 0) {
-         if (!defer_sync) CHK(hipk_wait_results(s->ctx));
-      } else {
-         CHK(hipk_d2h(s->ctx, s->h_red + (d_buf - s->d_red), d_buf, (size_t)count * sizeof(double)));
-         if (!defer_sync) CHK(hipk_sync(s->ctx));
-      }
-      }
-      }
-      if (!defer_sync && pa_comm_failed(p->commInfo)) return PRIMME_PARALLEL_FAILURE;
-   } else {
-      /* the reduction kernels already stored the local sums in h_red (zero-copy mirror) */
-      if (parallel) {
-         CHK(hipk_sync(s->ctx));
-         double *hb = s->h_red + (d_buf - s->d_red);
-         CHK(pa_call_global_sum(p, hb, count));
-         if (keep_dev) CHK(hipk_h2d(s->ctx, d_buf, hb, (size_t)count * sizeof(double)));
-      } else if (!defer_sync) {
-         /* the reduction whose result is wanted was the last launch: wait for its completion flag */
-         CHK(hipk_wait_results(s->ctx));
-      }
-   }
-   if (parallel) {
-      p->stats.numGlobalSum++;
-      p->stats.volumeGlobalSum += count;
-      p->stats.timeGlobalSum += pa_wtime() - t0;
-   }
-   return 0;
-}
-
-/* global sum of a few host scalars (cost-model ratios): through the same path as the
- * device partials so that every communicator flavour is covered */
-/* G = W(:,0:k)' Q for the locked / constraint vectors Q (projection column from W'r,
- * eigs_conv.c): one TN panel product after a restart. */
-int pa_refresh_wtq(pa_solver *s, int basisSize, int nLk) {
-   if (s->fov_carry && s->wtq_rows == basisSize && s->wtq_L == nLk) return 0;   /* the restart transformed it */
-   s->wtq_rows = -1; s->wtq_L = nLk;
-   if (!s->wtr_enabled || !s->wtq || basisSize > HIPK_WTR_MAX_K || nLk > HIPK_WTR_MAX_K) return 0;
-   if (nLk > 0 && basisSize > 0) {
-      if (basisSize * nLk > s->red_cap) return 0;
-      hipk_seg seg = {s->W, s->ld, basisSize};
-      CHK(hipk_panel_dots(s->ctx, s->dt, s->m, &seg, 1, s->evecs, s->ldevecs, nLk, s->d_red, basisSize));
-      CHK(pa_reduce(s, s->d_red, basisSize * nLk, 0, 0));
-      for (int l = 0; l < nLk; l++)
-         for (int j = 0; j < basisSize; j++) s->wtq[j + (size_t)l * s->K] = s->h_red[j + (size_t)l * basisSize];
-   }
-   s->wtq_rows = basisSize;
-   return 0;
-}
-
-int pa_trace_errors(void) {
-   static int on = -1;
-   if (on < 0) on = getenv("PRIMME_AMD_TRACE_ERRORS") != NULL;
-   return on;
-}
-
-int pa_reduce_host(pa_solver *s, double *buf, int count) {
-   if (count <= 0 || !s->parallel) return 0;
-   CHK(hipk_sync(s->ctx));
-   memcpy(s->h_red, buf, (size_t)count * sizeof(double));
-   if (s->dev_comm) CHK(hipk_h2d(s->ctx, s->d_red, s->h_red, (size_t)count * sizeof(double)));
-   CHK(pa_reduce(s, s->d_red, count, 0, 0));
-   memcpy(buf, s->h_red, (size_t)count * sizeof(double));
-   return 0;
-}
-
-#endif   /* !PA_IS_COMPLEX */
-#if PA_IS_COMPLEX
-double pa_problem_norm(int overrideUser, const primme_params *p);
-int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync);
-int pa_matvec(pa_solver *s, char *Vp, int64_t ldV, char *Wp, int64_t ldW, int c0, int nc);
-int pa_precond(pa_solver *s, char *X, int64_t ldX, char *Y, int64_t ldY, int nc);
-#else
-/* ---- W(:,c0:c0+nc) = A * V(:,c0:c0+nc)  (reference auxiliary_eigs.c:183-230) ---- */
-int pa_matvec(pa_solver *s, char *Vp, int64_t ldV, char *Wp, int64_t ldW, int c0, int nc) {
-   primme_params *p = s->p;
-   if (nc <= 0) return 0;
-   double t0 = pa_wtime();
-   int ierr = 0;
-   PRIMME_INT ldx = ldV, ldy = ldW;
-   p->matrixMatvec(PCOL(s, Vp, ldV, c0), &ldx, PCOL(s, Wp, ldW, c0), &ldy, &nc, p, &ierr);
-   if (ierr) return PRIMME_USER_FAILURE;
-   if (s->phase_timing) CHK(hipk_sync(s->ctx));
-   p->stats.timeMatvec += pa_wtime() - t0;
-   p->stats.numMatvecs += nc;
-   return 0;
-}
-
-/* ---- Y(:,0:nc) = B * X(:,0:nc)  (reference massMatrixMatvec_Sprimme, auxiliary_eigs.c:250-290) ---- */
-int pa_apply_B(pa_solver *s, char *X, int64_t ldX, char *Y, int64_t ldY, int nc) {
-   primme_params *p = s->p;
-   if (nc <= 0) return 0;
-   double t0 = pa_wtime();
-   /* in blocks of the width the callback was promised (maxBlockSize; the initial basis hands over more at once, init.c:210) */
-   int ierr = 0;
-   PRIMME_INT ldx = ldX, ldy = ldY;
-   p->massMatrixMatvec(X, &ldx, Y, &ldy, &nc, p, &ierr);
-   if (ierr) return PRIMME_USER_FAILURE;
-   if (s->phase_timing) CHK(hipk_sync(s->ctx));
-   p->stats.timeMatvec += pa_wtime() - t0;
-   p->stats.numMatvecs += nc;      /* the reference counts applications of B with those of A (auxiliary_eigs.c:283) */
-   return 0;
-}
-
-/* ---- y = K^-1 x or copy (reference auxiliary_eigs.c:317-364) -------------------- */
-int pa_precond(pa_solver *s, char *X, int64_t ldX, char *Y, int64_t ldY, int nc) {
-   primme_params *p = s->p;
-   if (nc <= 0) return 0;
-   double t0 = pa_wtime();
-   if (p->correctionParams.precondition) {
-      int ierr = 0;
-      PRIMME_INT ldx = ldX, ldy = ldY;
-      p->applyPreconditioner(X, &ldx, Y, &ldy, &nc, p, &ierr);
-      if (ierr) return PRIMME_USER_FAILURE;
-      p->stats.numPreconds += nc;
-   } else {
-      CHK(hipk_copy_cols(s->ctx, s->dt, s->m, X, ldX, Y, ldY, nc));
-   }
-   if (s->phase_timing) CHK(hipk_sync(s->ctx));
-   p->stats.timePrecond += pa_wtime() - t0;
-   return 0;
-}
-
-#endif
 /* random column (reference blaslapack.c:938-988 Num_larnv: host xLARNV then upload; complex entries take two
  * consecutive numbers of the stream, (re, im), as zlarnv does) */
 int pa_random_col(pa_solver *s, char *col) {
@@ -460,9 +286,7 @@ int pa_solve_H_RR(pa_solver *s, const HS *H, int ldH, const HS *VtBV, int ldVtBV
    return 0;
 }
 
-int pa_solve_H_harm(pa_solver *s, int k, const HS *G, int ldG);
-int pa_solve_H_ref(pa_solver *s, int k, double *hVals_out);
-
+/* ---- the projected problem by the extraction in use, and the running estimates of the spectrum edges ---- */
 int pa_solve_H(pa_solver *s, int basisSize, int numLocked, int numConverged) {
    primme_params *p = s->p;
    const int off = p->numOrthoConst + numLocked;

@@ -18,31 +18,6 @@
 #include <string.h>
 #include <assert.h>
 
-double pa_problem_norm(int overrideUser, const primme_params *p);
-int pa_ritz_update(pa_solver *s, int basisSize, const hipk_job *jobs, int njobs, double *norms_out,
-      int nslots, int64_t flop_cols);
-int pa_push_coefficients(pa_solver *s, int basisSize, int ldh);
-int pa_check_convergence(pa_solver *s, char *X, int64_t ldX, int givenX, char *R, int64_t ldR,
-      int givenR, int numLocked, int left, int right, int *flags, double *blockNorms,
-      const double *hVals, int *reset, int practConvCheck);
-int pa_ortho_local_vec(HS *x, int n, const HS *Q, int ldQ, int nQ, const HS *G,
-      int ldG, double *R, int64_t iseed[4]);
-int pa_solve_H_RR(pa_solver *s, const HS *H, int ldH, const HS *VtBV, int ldVtBV,
-      HS *hVecs, int ldhVecs, double *hVals, int n, int numConverged);
-void pa_monitor(pa_solver *s, double *basisEvals, int basisSize, int *basisFlags, int *iblock,
-      int blockSize, double *basisNorms, int numConverged, double *lockedEvals, int numLocked,
-      int *lockedFlags, double *lockedNorms, primme_event event);
-
-int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync);
-int pa_speculative_tail(pa_solver *s, int basisSize, int nLk, const char *rsrc, char *dstc, int nfov, int wtr,
-      int speculate2, int parallel_host, int col, int adopted);
-int pa_restart_harmonic(pa_solver *s, int ldh, int restartSize, int basisSize, int numConverged);
-int pa_restart_refined(pa_solver *s, int ldh, int restartSize, int basisSize, int numConverged, int numPrevRetained,
-      int indexOfPreviousVecs, int indexOfPreviousVecsBeforeRestart, const int *restartPerm, const int *hVecsPerm,
-      int *numArbitraryVecs);
-int pa_solve_H(pa_solver *s, int basisSize, int numLocked, int numConverged);
-int pa_update_cholesky(const HS *G, int ldG, HS *fG, int ldfG, int n0, int n);
-
 /* explicit_I: after V <- V*h, W <- W*h recompute from the data the Gram block G = V'V and
  * H = V'W of the restarted basis (reference auxiliary_eigs_normal.c:296-309 does it inside the
  * fused update) and rotate the locked-vs-basis block of VtBV on the host

@@ -4,9 +4,14 @@
  * eigs_restart.c, eigs_block.c, eigs_dense.c, eigs_jd.c, eigs_harm.c) are compiled twice, like the reference's templated sources: once
  * as they are (HS = double: hip_dprimme / hip_sprimme) and once with PA_COMPLEX defined (HS = double complex:
  * the native path of hip_zprimme / hip_cprimme) through the one-line wrappers eigs_*_z.c.  In the complex
- * objects every external function of those files carries the suffix _z (the list below is checked by the
- * linker: a missing entry is a duplicate symbol).  eigs_dynamic.c (timings and cost ratios of the dynamic method
- * switch, nothing scalar-typed) and the parameter / callback plumbing exist once and serve both.
+ * objects every external function of those files carries the suffix _z (the list below is checked in both
+ * directions: a missing entry is a duplicate symbol at link time, an entry for a function that exists once is an
+ * undefined pa_x_z, refused by the link's --no-undefined and named by tests/test_host_symbols.py).  Everything that
+ * does not depend on HS exists once and serves both: eigs_common.c (clock, problem norm, reductions, the operator
+ * wrappers, default convergence test, monitor, real / integer permutations, random numbers), eigs_dynamic.c (timings
+ * and cost ratios of the dynamic method switch) and the parameter / callback plumbing.  So a twice-built file holds no
+ * definition fenced off from the complex object only to keep it single: where PA_IS_COMPLEX is tested there, it
+ * selects real or complex arithmetic, or fences real-only code that works on HS (the fused block-size-1 paths).
  *
  * Device-layer conventions for complex panels (include/primme_amd_kernels.h): inner products, projection
  * coefficients, Ritz coefficient vectors and axpy factors are (re, im) pairs; Ritz values, shifts, squared

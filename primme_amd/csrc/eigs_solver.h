@@ -153,19 +153,134 @@ typedef struct pa_solver {
 #define TCOL(s, j) PCOL(s, (s)->T, (s)->ld, j)
 #define ECOL(s, j) PCOL(s, (s)->evecs, (s)->ldevecs, j)
 
-/* error propagation; with PRIMME_AMD_TRACE_ERRORS set the failing call chain is printed, the
- * counterpart of the reference's CHKERR trace (src/include/common.h:437-470) */
 /* an iteration enqueued ahead of the host is not going to be used: forget it and the tail it left unfinished (eigs_conv.c) */
 static inline void pa_pre_discard(pa_solver *s) {
    if (s->pre_valid && s->pre_tail_deferred) hipk_tail_abandon(s->ctx);
    s->pre_valid = 0; s->pre_tail_deferred = 0;
 }
-int pa_apply_B(pa_solver *s, char *X, int64_t ldX, char *Y, int64_t ldY, int nc);
+
+/* error propagation; with PRIMME_AMD_TRACE_ERRORS set the failing call chain is printed, the
+ * counterpart of the reference's CHKERR trace (src/include/common.h:437-470) */
 int pa_trace_errors(void);
 #define CHK(call) do { int rc_ = (call); if (rc_) { \
       if (pa_trace_errors()) fprintf(stderr, "primme_amd: error %d at %s:%d: %s\n", rc_, __FILE__, __LINE__, #call); \
       return rc_ < 0 ? rc_ : PRIMME_UNEXPECTED_FAILURE; } } while (0)
 
+/* The solver's steps, by the file that defines them.  A name on the _z list of eigs_scalar.h exists twice (real and
+ * complex objects); the others exist once and serve both. */
+
+/* ---- eigs_common.c */
 double pa_wtime(void);
+/* global sums of `count` partial sums in d_buf (device) into s->h_red, and into d_buf as well if keep_dev */
+int pa_reduce(pa_solver *s, double *d_buf, int count, int keep_dev, int defer_sync);
+/* global sum of a few host scalars through the same path */
+int pa_reduce_host(pa_solver *s, double *buf, int count);
+/* G = W(:,0:k)' Q for the locked / constraint vectors Q (projection column from W'r) */
+int pa_refresh_wtq(pa_solver *s, int basisSize, int nLk);
+/* W(:,c0:c0+nc) = A * V(:,c0:c0+nc) */
+int pa_matvec(pa_solver *s, char *Vp, int64_t ldV, char *Wp, int64_t ldW, int c0, int nc);
+/* Y(:,0:nc) = B * X(:,0:nc) */
+int pa_apply_B(pa_solver *s, char *X, int64_t ldX, char *Y, int64_t ldY, int nc);
+/* y = K^-1 x or copy */
+int pa_precond(pa_solver *s, char *X, int64_t ldX, char *Y, int64_t ldY, int nc);
+/* primme->monitorFun, or the reference's default report */
+void pa_monitor(pa_solver *s, double *basisEvals, int basisSize, int *basisFlags, int *iblock,
+      int blockSize, double *basisNorms, int numConverged, double *lockedEvals, int numLocked,
+      int *lockedFlags, double *lockedNorms, primme_event event);
+
+/* ---- eigs_ops.c */
+/* random column from the solver's seed stream */
+int pa_random_col(pa_solver *s, char *col);
+/* classical Gram-Schmidt with reorthogonalisation of Vp(:, b1..b2) against Vp(:, 0..b1-1) and `locked` */
+int pa_ortho_cgs(pa_solver *s, char *Vp, int64_t ldV, int b1, int b2, char *locked,
+      int64_t ldLocked, int numLocked, HS *RLocked, int ldRLocked, int *b2_out);
+/* H(:, k:k+b) = V(:,0:k+b)' W(:,k:k+b) */
+int pa_update_projection(pa_solver *s, int numCols, int blockSize);
+/* Rayleigh-Ritz on the projected matrix, eigenpairs ordered by primme->target */
+int pa_solve_H_RR(pa_solver *s, const HS *H, int ldH, const HS *VtBV, int ldVtBV,
+      HS *hVecs, int ldhVecs, double *hVals, int n, int numConverged);
+/* the projected problem by the extraction in use, and the running estimates of the spectrum edges */
+int pa_solve_H(pa_solver *s, int basisSize, int numLocked, int numConverged);
+/* upload the current coefficient vectors / Ritz values once per solve_H */
+int pa_push_coefficients(pa_solver *s, int basisSize, int ldh);
+/* one fused pass over V and W: the jobs' linear combinations and the squared norms of the residual jobs */
+int pa_ritz_update(pa_solver *s, int basisSize, const hipk_job *jobs, int njobs, double *norms_out,
+      int nslots, int64_t flop_cols);
+
+/* ---- eigs_block.c */
+/* explicit_I: orthonormalise a block with the tracked Gram matrix (iterative CholQR / SVQB) */
+int pa_ortho_block_gram(pa_solver *s, char *Vp, int64_t ldV, int b1, int b2, char *locked,
+      int64_t ldLocked, int numLocked, HS *RLocked, int ldRLocked, int maxRank, int *b2_out);
+
+/* ---- eigs_conv.c */
+/* X(:,inX) <- (I - Q Q') X(:,inX), norms of the result (one projector pass) */
+int pa_project_once(pa_solver *s, char *Q, int64_t ldQ, int nQ, char *X, int64_t ldX,
+      const int *inX, int nX, double *norms);
+/* flags[left..right) from blockNorms (indexed from 0), hVals indexed like flags. */
+int pa_check_convergence(pa_solver *s, char *X, int64_t ldX, int givenX, char *R, int64_t ldR,
+      int givenR, int numLocked, int left, int right, int *flags, double *blockNorms,
+      const double *hVals, int *reset, int practConvCheck);
+/* Put the first unconverged Ritz pairs in the block, computing X, R and the
+ * residual norms for them; flag converged pairs on the way. */
+int pa_prepare_candidates(pa_solver *s, int basisSize, char *X, char *R, int computeXR,
+      int *flags, int remainedEvals, double *blockNorms, int blockNormsSize, int maxBlockSize,
+      int numLocked, double *evals, double *resNorms, int *iev, int *blockSize,
+      int *recentlyConverged, double *smallestResNorm, int numConverged, double *basisNorms,
+      int *reset, int nprevhVecs, int practConvChecking, int *map);
+/* the fused block-size-1 tail: project the new vector, normalise it with the device-resident norm, apply the operator
+ * (real objects only) */
+int pa_speculative_tail(pa_solver *s, int basisSize, int nLk, const char *rsrc, char *dstc, int nfov, int wtr,
+      int speculate2, int parallel_host, int col, int adopted);
+
+/* ---- eigs_restart.c */
+/* thick restart with +k retained directions, soft and hard locking */
+int pa_restart(pa_solver *s, int basisSize, int *flags, int *iev, int *ievSize, double *blockNorms,
+      int *evecsPerm, double *evals, double *resNorms, int *numConverged, int *numLocked,
+      int *lockedFlags, int nprevhVecs, int numGuesses, int *restartSizeOutput,
+      int *restartsSinceReset);
+/* before a restart: converged pairs and the block first (coefficient vectors, Ritz values and flags alike) */
+int pa_block_first_reorder(pa_solver *s, int basisSize, int *flags, const int *iev, int blockSize, int numConverged,
+      int numLocked);
+/* dry run of the restart: predicts its coefficient block for "candidate not converged" (real objects only) */
+int pa_restart_plan(pa_solver *s, int basisSize, const int *flags_in, const int *iev_in, int nblock, int numLocked,
+      int nprevhVecs, const int *map, double *evals, double *resNorms);
+
+/* ---- eigs_harm.c: harmonic and refined extraction */
+/* Q(:, col0:col0+bs) = W - tau V for the new columns, then orthonormalised against Q(:, 0:*nQ) */
+int pa_update_Q(pa_solver *s, double tau, int col0, int bs, int *nQ);
+/* QtV(0:n1, col0:n1) and QtV(col0:n1, 0:col0), n1 = col0 + bs */
+int pa_update_QtV(pa_solver *s, int col0, int bs);
+/* harmonic Ritz pairs of the current basis: hVecs (k x k, ld k), hVals (Rayleigh quotients) */
+int pa_solve_H_harm(pa_solver *s, int k, const HS *G, int ldG);
+/* refined Ritz pairs: singular triplets of R */
+int pa_solve_H_ref(pa_solver *s, int k, double *hVals_out);
+/* hVecs(:, j:i-1) <- Rayleigh-Ritz vectors of the span of a cluster of singular vectors */
+int pa_prepare_vecs(pa_solver *s, int basisSize, int i0, int blockSize, int *arbitraryVecs, double smallestResNorm,
+      const int *flags, int RRForAll);
+/* after V, W <- V h, W h: projected matrix, fresh QR for the (possibly new) target shift */
+int pa_restart_harmonic(pa_solver *s, int ldh, int restartSize, int basisSize, int numConverged);
+int pa_restart_refined(pa_solver *s, int ldh, int restartSize, int basisSize, int numConverged, int numPrevRetained,
+      int indexOfPreviousVecs, int indexOfPreviousVecsBeforeRestart, const int *restartPerm, const int *hVecsPerm,
+      int *numArbitraryVecs);
+
+/* ---- eigs_jd.c: the JDQMR correction equation */
+int pa_evecs_hat_init(pa_solver *s);
+/* after a restart: K^-1 of the vectors that converged since the last call */
+int pa_evecs_hat_update(pa_solver *s, int *numConvergedStored, int numConverged);
+/* corrections of the block by inner QMR iterations; `shifts` are the correction-equation shifts of the caller */
+int pa_correction_jdqmr(pa_solver *s, int basisSize, int blockSize, const double *blockNorms, const int *iev,
+      double *shifts, int numLocked, int numConvergedStored, int *touch);
+
+/* ---- eigs_dynamic.c: the dynamic method's cost model */
+void pa_dyn_init(pa_cost_model *c, const primme_params *p);
+/* returns 1 when the model was updated and the methods may be compared */
+int pa_dyn_observe(pa_cost_model *c, primme_params *p, double now, int recentConv, int atRestart,
+      int numConverged, double currentResNorm);
+/* GD+k is running (state 1 or 3): move to JDQMR_ETol if it is expected to be faster */
+int pa_dyn_leave_gd(pa_solver *s, pa_cost_model *c);
+/* JDQMR_ETol is running (state 2 or 4) */
+int pa_dyn_leave_jdqmr(pa_solver *s, pa_cost_model *c);
+/* method recommendation for later runs, left in dynamicMethodSwitch */
+void pa_dyn_recommend(const pa_cost_model *c, primme_params *p);
 
 #endif

@@ -2,6 +2,7 @@
  * deterministic second stage of every reduction, and the bandwidth probe.
  * See include/primme_amd_kernels.h for the reference routines each entry replaces. */
 #include "hipk_internal.h"
+#include "eigs_internal.h"   /* hipk_xreduce_*: declared where the host solver, their only caller, sees them */
 #include <time.h>
 static double g_alloc_s = 0.0;      /* HIPK_HOST_TIMING: seconds spent in hipMalloc / hipFree */
 static long g_alloc_n = 0;

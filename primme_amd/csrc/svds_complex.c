@@ -75,8 +75,6 @@ static int sum_svds(void *who, double *buf, int count) { return pa_svds_call_glo
 
 #define CX(call) do { int rc__ = (call); if (rc__) { ret = rc__ < 0 ? rc__ : PRIMME_UNEXPECTED_FAILURE; goto done; } } while (0)
 
-int pa_svds_solve_native_complex(void *svals, void *svecs, void *resNorms, primme_svds_params *ps, int single);
-
 static int solve_svds_complex(void *svals_out, void *svecs_, void *resNorms_out, primme_svds_params *ps, hipk_dtype dtr) {
    if (!ps) return -4;
    if (!svals_out && !svecs_ && !resNorms_out)       /* defaults query: the same for every precision */

@@ -22,8 +22,6 @@
 #include "eigs_solver.h"
 #include "primme_amd_svds.h"
 
-int pa_eigs_solve(void *evals_out, void *evecs, void *resNorms_out, primme_params *p, hipk_dtype dt, int out_double);
-
 /* per-solve device state, found again from the callbacks through the params address */
 typedef struct {
    primme_svds_params *key;
@@ -55,7 +53,6 @@ static hipk_dtype rdt_of(hipk_dtype dt) { return dt == HIPK_C64 ? HIPK_F64 : dt 
 static size_t es_of(hipk_dtype dt) { return dt == HIPK_C64 ? 16 : (dt == HIPK_F64 || dt == HIPK_C32) ? 8 : 4; }
 #define RDT(sd) rdt_of((sd)->dt)
 #define RF(sd) ((PRIMME_INT)(is_cplx((sd)->dt) ? 2 : 1))
-int pa_eigs_solve_z(void *evals_out, void *evecs, void *resNorms_out, primme_params *p, hipk_dtype dt, int out_double);
 
 /* W(:, 0:nb) = A V or A' V through the user's operator (reference :1116-1172) */
 static int svds_matvec(primme_svds_params *ps, void *V, PRIMME_INT ldV, void *W, PRIMME_INT ldW, int nb, int transpose) {
@@ -72,7 +69,7 @@ static int svds_matvec(primme_svds_params *ps, void *V, PRIMME_INT ldV, void *W,
 static int true_res_norm(primme_svds_params *ps, svds_side *sd, char *u, char *v, double *rNorm);
 
 /* the eigensolver's operator: A'A x (method AtA), A A' x (method AAt) or [0 A'; A 0] x */
-void pa_svds_matvec_eigs(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy, int *blockSize,
+static void pa_svds_matvec_eigs(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy, int *blockSize,
       primme_params *primme, int *ierr) {
    primme_svds_params *ps = (primme_svds_params *)primme->matrix;
    svds_side *sd = side_of(ps);
@@ -110,7 +107,6 @@ void pa_svds_matvec_eigs(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy, int
 /* The one-synchronisation tail of the eigensolver's block-size-1 iteration (eigs_conv.c) for the normal equations
  * with the library's own operator on one rank: xout = a t (a = 1/sqrt(norm2_dev[0]), or t itself), u = A xout,
  * dot_dev[0] = xout'(A'A xout) = u'u, y = A'u -- everything enqueued, nothing waited for. */
-int primme_amd_svds_operator_is_local(const void *op);
 int pa_svds_can_fuse(const primme_params *primme) {
    if (primme->matrixMatvec != pa_svds_matvec_eigs || !primme->matrix) return 0;
    primme_svds_params *ps = (primme_svds_params *)primme->matrix;
@@ -151,7 +147,7 @@ static void pa_svds_precond_eigs(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *
 }
 
 /* |r| < max(eps, 3.16 machEps) |A|: the default test on a triplet */
-void pa_svds_default_conv_test(double *sval, void *leftsvec, void *rightsvec, double *rNorm, int *method,
+static void pa_svds_default_conv_test(double *sval, void *leftsvec, void *rightsvec, double *rNorm, int *method,
       int *isConv, primme_svds_params *ps, int *ierr) {
    (void)sval;
    svds_side *sd = side_of(ps);
@@ -167,9 +163,7 @@ void pa_svds_default_conv_test(double *sval, void *leftsvec, void *rightsvec, do
 }
 
 /* the eigensolver's convergence test: translate (eval, |r_eig|) to (sigma, |r_eig| / sigma) */
-void pa_larnv_uniform11(int64_t iseed[4], int64_t n, double *x);
-
-void pa_svds_conv_test_ata(double *eval, void *evec, double *rNorm, int *isConv, primme_params *primme, int *ierr) {
+static void pa_svds_conv_test_ata(double *eval, void *evec, double *rNorm, int *isConv, primme_params *primme, int *ierr) {
    primme_svds_params *ps = (primme_svds_params *)primme->matrix;
    svds_side *sd = side_of(ps);
    const primme_svds_operator op = (&ps->primme == primme) ? ps->method : ps->methodStage2;
@@ -333,7 +327,7 @@ static int true_res_norm(primme_svds_params *ps, svds_side *sd, char *u, char *v
 }
 
 /* the eigensolver's convergence test for the augmented operator (reference :1705-1745) */
-void pa_svds_conv_test_aug(double *eval, void *evec, double *rNorm, int *isConv, primme_params *primme, int *ierr) {
+static void pa_svds_conv_test_aug(double *eval, void *evec, double *rNorm, int *isConv, primme_params *primme, int *ierr) {
    primme_svds_params *ps = (primme_svds_params *)primme->matrix;
    const double aNorm = primme->aNorm > 0.0 ? primme->aNorm : primme->stats.estimateLargestSVal;
    *ierr = 0;

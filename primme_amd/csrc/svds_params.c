@@ -8,8 +8,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include "primme_amd_svds.h"
-
-int pa_svds_call_global_sum(primme_svds_params *ps, double *buf, int count);
+#include "eigs_internal.h"
 
 static void sum_via_svds(void *sendBuf, void *recvBuf, int *count, primme_params *primme, int *ierr) {
    /* installed with globalSumReal_type = double (the eigensolver reduces doubles); the user's own
