@@ -316,6 +316,33 @@ int primme_amd_operator_gershgorin(struct primme_amd_operator *op, double *lo, d
 void primme_amd_chebyshev_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
       int *blockSize, struct primme_params *primme, int *ierr);
 void primme_amd_chebyshev_stats(long *applies, long *operator_products, long *fused_steps);
+/* Geometric multigrid preconditioner for grid Laplacians (no reference counterpart): y = K^-1 x is ONE
+ * symmetric V(smooth_steps, smooth_steps) cycle from a zero start for
+ *    M = scale L + shift I,
+ * L the Dirichlet Laplacian of the nx x ny x nz grid that hipk_stencil_create represents (x fastest, off-diagonals -1, diagonal
+ * 2 per dimension with more than one point).  K does not follow the solver's shifts and is symmetric positive definite, whatever
+ * the operator of the eigenproblem is: the stencil form, a CSR Laplacian, or -Laplacian + V with shift about the mean of V.
+ *    primme_amd_operator_set_multigrid(op, nx, ny, nz, smooth_steps, coarse_steps, scale, shift)
+ * then primme->preconditioner = the operator handle and primme->applyPreconditioner = primme_amd_multigrid_precond.
+ * Levels: primme_amd_mg_plan (level 0 = the grid with weights 1; a dimension of 3 or more points is halved, coarse point j on
+ * fine point 2 j + 1, its weight divided by 4; the last level has no such dimension or at most PRIMME_AMD_MG_COARSE_POINTS
+ * points).  Level operator M_l = scale sum_d w_l,d L_d + shift I (rediscretised).  Transfers: tensor products of 1-D linear
+ * interpolation P_d (identity in a dimension that is kept) and R_d = P_d' / 2.  Smoother: smooth_steps steps of the Chebyshev
+ * iteration for M_l on [hi_l / (2 D_l), hi_l], hi_l the exact largest eigenvalue and D_l the number of dimensions with more
+ * than one point, the same polynomial before (from zero) and after (from the corrected iterate) the coarse correction.  Last
+ * level: coarse_steps Chebyshev steps over its exact spectrum.  Kernels: csrc/hipk_mg.hip.
+ * set_multigrid returns -44 for a row-partitioned operator, a complex operator or the real-equivalent mode, -1 for nx ny nz !=
+ * the operator's rows, steps < 1, scale <= 0, shift < 0 (or a singular M: one grid point and shift = 0).  The level scratch is
+ * allocated at the first application and freed with the operator; block columns beyond 8 are processed in chunks.
+ * primme_amd_multigrid_stats: for this process since the last call, the vectors preconditioned and the kernel launches. */
+#define PRIMME_AMD_MG_MAXLEVELS 24
+#define PRIMME_AMD_MG_COARSE_POINTS 32
+int primme_amd_mg_plan(const int dims[3], int *nlevels, int n[][3], double w[][3]);
+int primme_amd_operator_set_multigrid(struct primme_amd_operator *op, int nx, int ny, int nz, int smooth_steps, int coarse_steps,
+      double scale, double shift);
+void primme_amd_multigrid_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
+      int *blockSize, struct primme_params *primme, int *ierr);
+void primme_amd_multigrid_stats(long *applies, long *launches);
 /* globalSumReal over RCCL: set primme->commInfo = handle from primme_amd_comm_create().
  * When the solver sees this exact function installed it reduces its DEVICE partials
  * with ncclAllReduce before the (single) device->host copy; called directly it also

@@ -443,6 +443,27 @@ int hipk_csr_cheb_step_gather(hipk_csr *A, void *hip_stream, int nx, const hipk_
       const void *G, int64_t ldg, const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp, void *Out, int64_t ldo);
 int hipk_csr_abs_rowsum_max(hipk_csr *A, void *hip_stream, double *out);
 
+/* ---- geometric multigrid on a grid (csrc/hipk_mg.hip; primme_amd_multigrid_precond, no reference counterpart) -----------
+ * Matrix-free pieces of a V-cycle for panels of nx <= HIPK_CHEB_MAXCOLS columns on an n[0] x n[1] x n[2] grid, x fastest,
+ * n[0] n[1] n[2] <= INT32_MAX points; HIPK_F64 / HIPK_F32 (complex: -44), the arithmetic in double.  Leading dimensions are
+ * free; an access moves 16 bytes where every streamed panel is 16-byte aligned (base and leading dimension), one element
+ * where not; neighbours come from cache.
+ *   hipk_mg_stencil_step   Out = cx X + cy Yk + cp Yprev + cw (sum_d w[d] L_d Yk), L_d the 1-D Dirichlet Laplacian (2, -1) along
+ *                          dimension d; a dimension with n[d] = 1 is absent.  Coefficients per column as in hipk_csr_cheb_step.
+ *                          Yk and Yprev may each be NULL (the term is left out); Out may be X or Yprev, never Yk (other points
+ *                          read it).  A Chebyshev step, or the residual b - M y (cx = 1, cy = -shift, cw = -scale), of
+ *                          M = scale sum_d w[d] L_d + shift I.
+ *   hipk_mg_restrict       C = R F from the grid nf to the grid nc, nc[d] = nf[d] / 2 where nf[d] >= 3 (coarse j on fine 2 j + 1:
+ *                          c_j = f_2j / 4 + f_2j+1 / 2 + f_2j+2 / 4, a point outside counts 0), else nc[d] = nf[d] (identity)
+ *   hipk_mg_prolong_add    Y += P C, P linear interpolation: fine 2 j + 1 takes c_j, fine 2 j takes (c_j-1 + c_j) / 2
+ * -1: argument error (nc is not the coarse grid of nf included). */
+int hipk_mg_stencil_step(void *hip_stream, hipk_dtype dt, const int n[3], const double w[3], int nx, const hipk_cheb_coef *coef,
+      const void *X, int64_t ldx, const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp, void *Out, int64_t ldo);
+int hipk_mg_restrict(void *hip_stream, hipk_dtype dt, const int nf[3], const int nc[3], int nx, const void *F, int64_t ldf,
+      void *C, int64_t ldc);
+int hipk_mg_prolong_add(void *hip_stream, hipk_dtype dt, const int nf[3], const int nc[3], int nx, const void *C, int64_t ldc,
+      void *Y, int64_t ldy);
+
 /* ---- Rayleigh-Ritz small solve on the device (reference solve_projection.c:188-331 calls xHEEVX,
  * blaslapack.c:1024-1143).  Symmetric n x n (n <= 64), upper triangle of A_host referenced;
  * eigenvalues ascending in evals_host, orthonormal eigenvectors in Z_host.  One workgroup, parallel

@@ -318,6 +318,27 @@ def declare_chebyshev(lib):
     lib.hipk_csr_abs_rowsum_max.restype = C.c_int
 
 
+def declare_multigrid(lib):
+    """The geometric multigrid preconditioner (include/primme_amd.h) and its kernels (csrc/hipk_mg.hip): product library only;
+    primme_amd_mg_plan is host code that the CPU checker build has too (tests/mg_cases.py declares it there)."""
+    P = C.POINTER
+    i3, d3 = P(_i), _dp
+    lib.primme_amd_mg_plan.argtypes = [i3, P(_i), _vp, _vp]
+    lib.primme_amd_mg_plan.restype = C.c_int
+    lib.primme_amd_operator_set_multigrid.argtypes = [_vp, _i, _i, _i, _i, _i, C.c_double, C.c_double]
+    lib.primme_amd_operator_set_multigrid.restype = C.c_int
+    lib.primme_amd_multigrid_precond.argtypes = [_vp, P(PRIMME_INT), _vp, P(PRIMME_INT), P(_i), _vp, P(_i)]
+    lib.primme_amd_multigrid_precond.restype = None
+    lib.primme_amd_multigrid_stats.argtypes = [P(C.c_long), P(C.c_long)]
+    lib.primme_amd_multigrid_stats.restype = None
+    lib.hipk_mg_stencil_step.argtypes = [_vp, _i, i3, d3, _i, P(HipkChebCoef), _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]
+    lib.hipk_mg_stencil_step.restype = C.c_int
+    lib.hipk_mg_restrict.argtypes = [_vp, _i, i3, i3, _i, _vp, _i64, _vp, _i64]
+    lib.hipk_mg_restrict.restype = C.c_int
+    lib.hipk_mg_prolong_add.argtypes = [_vp, _i, i3, i3, _i, _vp, _i64, _vp, _i64]
+    lib.hipk_mg_prolong_add.restype = C.c_int
+
+
 def declare_formats(lib):
     """Creation with options and the queries of the one-column product's form: product library only (the CPU checker has one form)."""
     P = C.POINTER
@@ -371,6 +392,7 @@ def load_product():
         declare_solver(lib, "hip_")
         declare_kernels(lib)
         declare_chebyshev(lib)
+        declare_multigrid(lib)
         declare_formats(lib)
         _cache["product"] = lib
     return _cache["product"]

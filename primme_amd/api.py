@@ -66,7 +66,8 @@ class Result:
         self.params = {k: getattr(params, k) for k in ("maxBasisSize", "minRestartSize", "maxBlockSize",
                                                        "locking", "orth", "aNorm", "eps", "initSize", "dynamicMethodSwitch")}
         self.params["maxPrevRetain"] = params.restartingParams.maxPrevRetain
-        # Chebyshev preconditioner only: {"applies", "operator_products", "fused_steps"} of this solve (counted in vectors)
+        # Chebyshev preconditioner: {"applies", "operator_products", "fused_steps"} of this solve (counted in vectors);
+        # multigrid preconditioner: {"applies", "launches"} (vectors, kernel launches)
         self.precond_stats = None
 
 
@@ -211,6 +212,19 @@ class Session:
                                  f"library; back end {self.backend!r} has no such operator")
             if user_precond is not None:
                 raise ValueError("precond=('chebyshev', ...) and user_precond exclude each other")
+        mg = isinstance(precond, (tuple, list)) and len(precond) > 0 and precond[0] == "multigrid"
+        if mg:
+            if not 2 <= len(precond) <= 6:
+                raise ValueError("precond: ('multigrid', dims[, smooth_steps[, coarse_steps[, scale[, shift]]]])")
+            if not (self.be.native_operator and hasattr(lib, "primme_amd_multigrid_precond")):
+                raise ValueError(f"precond={precond!r}: the multigrid preconditioner runs on the device operator of the product "
+                                 f"library; back end {self.backend!r} has no such operator")
+            if user_precond is not None:
+                raise ValueError("precond=('multigrid', ...) and user_precond exclude each other")
+            if self.cplx:
+                raise ValueError(f"precond={precond!r}: the multigrid preconditioner serves real operators")
+            if self.comm is not None:
+                raise ValueError(f"precond={precond!r}: the multigrid preconditioner serves single-rank operators")
         p = F.PrimmeParams()
         nLocal = op.nrows
         v0 = None if v0 is None else np.asarray(v0, dtype=dtype).reshape(nLocal, -1)
@@ -285,6 +299,24 @@ class Session:
                 p.preconditioner = self.oph
                 p.applyPreconditioner = C.cast(lib.primme_amd_chebyshev_precond, C.c_void_p)
                 p.correctionParams.precondition = 1
+            elif mg:
+                # ("multigrid", dims[, smooth_steps[, coarse_steps[, scale[, shift]]]]): one V-cycle for scale * Laplacian + shift
+                dims = tuple(int(d) for d in precond[1])
+                if not 1 <= len(dims) <= 3:
+                    raise ValueError(f"precond={precond!r}: dims holds one to three grid lengths, x first")
+                nx, ny, nz = (list(dims) + [1, 1])[:3]
+                nu = int(precond[2]) if len(precond) > 2 else 2
+                ncs = int(precond[3]) if len(precond) > 3 else 16
+                scale = float(precond[4]) if len(precond) > 4 else 1.0
+                shift = float(precond[5]) if len(precond) > 5 else 0.0
+                rc = lib.primme_amd_operator_set_multigrid(self.oph, nx, ny, nz, nu, ncs, scale, shift)
+                if rc:
+                    raise ValueError(f"precond={precond!r}: needs a real single-rank operator ({rc}), prod(dims) = its rows, "
+                                     "steps >= 1, scale > 0 and shift >= 0")
+                lib.primme_amd_multigrid_stats(None, None)            # the counters are per process: start this solve at zero
+                p.preconditioner = self.oph
+                p.applyPreconditioner = C.cast(lib.primme_amd_multigrid_precond, C.c_void_p)
+                p.correctionParams.precondition = 1
             elif precond is not None:
                 # "jacobi": per-vector shifts of the solver; ("jacobi", s): fixed K = diag(A) - s
                 if precond == "jacobi": lib.primme_amd_operator_set_jacobi(self.oph, 0, 0.0)
@@ -357,6 +389,10 @@ class Session:
             st = [C.c_long(0), C.c_long(0), C.c_long(0)]
             lib.primme_amd_chebyshev_stats(*[C.byref(v) for v in st])
             res.precond_stats = dict(zip(("applies", "operator_products", "fused_steps"), (v.value for v in st)))
+        if mg:
+            st = [C.c_long(0), C.c_long(0)]
+            lib.primme_amd_multigrid_stats(*[C.byref(v) for v in st])
+            res.precond_stats = dict(zip(("applies", "launches"), (v.value for v in st)))
         return res
 
 
@@ -368,6 +404,9 @@ def eigsh(op, backend="hip", comm=None, dtype=np.float64, complex_form="native",
     precond: None | "jacobi" (Davidson: per-vector shifts) | ("jacobi", shift) (fixed shift) |
     ("chebyshev", steps, lo[, hi]) (polynomial preconditioner with the solver's shifts; hi defaults to the Gershgorin
     bound) | ("chebyshev", steps, lo, hi, shift) (fixed shift).  Result.precond_stats then holds its counters.
+    ("multigrid", dims[, smooth_steps[, coarse_steps[, scale[, shift]]]]): one geometric multigrid V-cycle for
+    scale * Laplacian + shift on the grid dims = (nx[, ny[, nz]]), x fastest (defaults 2, 16, 1, 0), for grid Laplacians in any
+    operator form and for -Laplacian + V with shift about the mean of V; Result.precond_stats = {"applies", "launches"}.
     members: {"name": value} set through primme_set_member after the method preset and before `tweak`, e.g.
     {"correctionParams.maxInnerIterations": 0, "projectionParams.projection": "primme_proj_refined"}; a string for an
     enum member is an enumerator name (primme_constant_info); an unknown member or enumerator is a ValueError.

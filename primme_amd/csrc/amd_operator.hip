@@ -32,6 +32,15 @@ struct primme_amd_operator {
                                 operator product of the generic path (cheb_cols columns), cheb_ld elements apart */
    int cheb_cols, cheb_wcols;
    int64_t cheb_ld;
+   /* geometric multigrid preconditioner (primme_amd_multigrid_precond): mg_nlev = 0 until configured.  Level l has the grid
+      mg_n[l] with weights mg_w[l], mg_ld[l] elements per scratch column (16-byte columns) and, in ONE allocation of mg_cols
+      columns per panel, a temporary (level 0; the other iterate is the caller's y) or the right-hand side and two iterates */
+   int mg_nlev, mg_nu, mg_cs, mg_cols;
+   double mg_scale, mg_shift;
+   int mg_n[PRIMME_AMD_MG_MAXLEVELS][3];
+   double mg_w[PRIMME_AMD_MG_MAXLEVELS][3];
+   int64_t mg_ld[PRIMME_AMD_MG_MAXLEVELS];
+   void *mg_buf;
 };
 
 static size_t op_elem(hipk_dtype dt) { return dt == HIPK_F64 ? 8 : dt == HIPK_F32 ? 4 : dt == HIPK_C64 ? 16 : 8; }
@@ -90,6 +99,7 @@ extern "C" int primme_amd_operator_destroy(primme_amd_operator *op) {
    if (op->xfull) (void)hipFree(op->xfull);
    if (op->cheb_y) (void)hipFree(op->cheb_y);
    if (op->cheb_w) (void)hipFree(op->cheb_w);
+   if (op->mg_buf) (void)hipFree(op->mg_buf);
    free(op);
    return 0;
 }
@@ -368,6 +378,175 @@ extern "C" void primme_amd_chebyshev_precond(void *x, PRIMME_INT *ldx, void *y, 
          if (rc) *ierr = 1;
       }
    }
+}
+
+/* ---- geometric multigrid preconditioner for grid Laplacians (kernels in hipk_mg.hip) --------------------
+ * y = K^-1 x: one symmetric V(nu, nu) cycle from zero for M = scale L + shift I on the grid given to set_multigrid,
+ *    vcycle(l, b):  l == last: nu_c Chebyshev steps from zero over the exact spectrum of M_l
+ *                   y = nu Chebyshev steps from zero;  y += P vcycle(l + 1, R (b - M_l y));  nu Chebyshev steps from y
+ * with the smoother's interval [hi_l / (2 D_l), hi_l].  The post-smoother is the SAME iteration started at y (first step
+ * y + (b - M y) / tb): with p the smoother's polynomial it returns y + p(M)(b - M y), which makes K symmetric, in nu passes
+ * instead of a residual, nu - 1 steps and an update.  Every pass is one hipk_mg_stencil_step: a Chebyshev step (coefficients of
+ * cheb_step_coef with sigma = -shift, the product's scaled by `scale`) or the residual.  Per level the iterates alternate
+ * between two panels, y_{k+1} over y_{k-1}; which of the two a sequence starts in is chosen so that its last iterate lands
+ * where the next stage expects it (level 0: in the caller's y). */
+static long g_mg_applies, g_mg_launches;
+extern "C" void primme_amd_multigrid_stats(long *applies, long *launches) {
+   if (applies) *applies = g_mg_applies;
+   if (launches) *launches = g_mg_launches;
+   g_mg_applies = g_mg_launches = 0;
+}
+
+/* exact ends of the spectrum of M_l and D_l, the number of dimensions with more than one point */
+static void mg_level_ends(const primme_amd_operator *op, int l, double *lo, double *hi, int *D) {
+   double a = 0.0, b = 0.0;
+   int nd = 0;
+   for (int d = 0; d < 3; d++)
+      if (op->mg_n[l][d] > 1) {
+         const double c = cos(M_PI / (op->mg_n[l][d] + 1));
+         a += op->mg_w[l][d] * (2.0 - 2.0 * c);
+         b += op->mg_w[l][d] * (2.0 + 2.0 * c);
+         nd++;
+      }
+   *lo = op->mg_scale * a + op->mg_shift; *hi = op->mg_scale * b + op->mg_shift; *D = nd;
+}
+
+extern "C" int primme_amd_operator_set_multigrid(primme_amd_operator *op, int nx, int ny, int nz, int smooth_steps, int coarse_steps,
+      double scale, double shift) {
+   if (!op) return -1;
+   const hipk_dtype dt = hipk_csr_dtype(op->A);
+   if (op->mode != 0 || (op->comm && primme_amd_comm_size(op->comm) > 1) || op->ldscale != 1 || (dt != HIPK_F64 && dt != HIPK_F32)) return -44;
+   if (nx < 1 || ny < 1 || nz < 1 || smooth_steps < 1 || coarse_steps < 1 || !(scale > 0.0) || !(shift >= 0.0)) return -1;
+   if ((int64_t)nx * ny > INT32_MAX || (int64_t)nx * ny * nz != hipk_csr_nrows(op->A)) return -1;
+   primme_amd_operator cand = *op;                 /* the operator changes only when everything is in order */
+   const int dims[3] = {nx, ny, nz};
+   if (primme_amd_mg_plan(dims, &cand.mg_nlev, cand.mg_n, cand.mg_w)) return -1;
+   cand.mg_nu = smooth_steps; cand.mg_cs = coarse_steps; cand.mg_scale = scale; cand.mg_shift = shift;
+   double lo, hi;
+   int D;
+   mg_level_ends(&cand, cand.mg_nlev - 1, &lo, &hi, &D);
+   if (!(lo > 0.0)) return -1;                     /* one grid point and no shift: M = 0 */
+   for (int l = 0; l < cand.mg_nlev; l++) cand.mg_ld[l] = ((int64_t)cand.mg_n[l][0] * cand.mg_n[l][1] * cand.mg_n[l][2] + 3) / 4 * 4;
+   if (op->mg_buf) (void)hipFree(op->mg_buf);      /* another grid: the scratch is laid out again at the next application */
+   cand.mg_buf = NULL; cand.mg_cols = 0;
+   *op = cand;
+   return 0;
+}
+
+struct mg_run {
+   primme_amd_operator *op;
+   void *stream;
+   hipk_dtype dt;
+   size_t es;
+   int nc;
+   int rc;
+};
+static void mg_step(mg_run *r, int l, const hipk_cheb_coef *cf, const char *x, int64_t lx, const char *yk, int64_t ldk, const char *yp,
+      int64_t ldp, char *out, int64_t ldo) {
+   if (r->rc) return;
+   r->rc = hipk_mg_stencil_step(r->stream, r->dt, r->op->mg_n[l], r->op->mg_w[l], r->nc, cf, x, lx, yk, ldk, yp, ldp, out, ldo);
+   g_mg_launches++;
+}
+/* `steps` steps of the Chebyshev iteration for M_l y = b on [lo, hi] with the iterates in B[0], B[1]: from zero when from < 0 (the
+ * result in B[to]), else from B[from].  Returns the index of the panel that holds the last iterate. */
+static int mg_cheb(mg_run *r, int l, double lo, double hi, int steps, const char *b, int64_t lb, char *const B[2], const int64_t LB[2],
+      int from, int to) {
+   const double scale = r->op->mg_scale, shift = r->op->mg_shift, tb = 0.5 * (hi + lo), dl = 0.5 * (hi - lo);
+   hipk_cheb_coef cf;
+   memset(&cf, 0, sizeof(cf));
+   if (from < 0 && (steps == 1 || !(dl > 0.0))) {               /* y_1 = b / tb (a one-point level: the exact solution) */
+      for (int c = 0; c < r->nc; c++) cf.cx[c] = 1.0 / tb;
+      mg_step(r, l, &cf, b, lb, NULL, 0, NULL, 0, B[to], LB[to]);
+      return to;
+   }
+   double rho = dl / tb;
+   if (from < 0) {
+      /* as in primme_amd_chebyshev_precond: y_1 = b / tb is never stored, step k = 1 .. steps - 1 writes y_{k+1} */
+      for (int k = 1; k < steps; k++) {
+         const int o = (to + (steps - 1 - k)) % 2;
+         for (int c = 0; c < r->nc; c++) {
+            double rc = rho;
+            cheb_step_coef(tb, dl, -shift, k, &rc, &cf, c);
+            cf.cw[c] *= scale;
+            if (c == r->nc - 1) rho = rc;
+         }
+         const char *yk = k == 1 ? b : B[1 - o], *yp = k == 1 ? NULL : (k == 2 ? b : B[o]);
+         mg_step(r, l, &cf, b, lb, yk, k == 1 ? lb : LB[1 - o], yp, k == 2 ? lb : LB[o], B[o], LB[o]);
+      }
+      return to;
+   }
+   /* from y_0 = B[from]: y_1 = y_0 + (b - M y_0) / tb, then the three-term steps; y_j goes to B[(from + j) % 2] */
+   for (int j = 1; j <= steps; j++) {
+      const int o = (from + j) % 2;
+      double cy, cp, cx, cw;
+      if (j == 1 || !(dl > 0.0)) { cy = 1.0 - shift / tb; cp = 0.0; cx = 1.0 / tb; cw = -scale / tb; }
+      else {
+         const double rn = 1.0 / (2.0 * tb / dl - rho), a = rn * rho, bb = 2.0 * rn / dl;
+         cy = 1.0 + a - bb * shift; cp = -a; cx = bb; cw = -bb * scale;
+         rho = rn;
+      }
+      for (int c = 0; c < r->nc; c++) { cf.cy[c] = cy; cf.cp[c] = cp; cf.cx[c] = cx; cf.cw[c] = cw; }
+      mg_step(r, l, &cf, b, lb, B[1 - o], LB[1 - o], (j == 1 || cp == 0.0) ? NULL : B[o], LB[o], B[o], LB[o]);
+   }
+   return (from + steps) % 2;
+}
+/* panel q (0: right-hand side, 1, 2: iterates) of level l >= 1; level 0 has only its temporary, q = 0 */
+static char *mg_panel(const primme_amd_operator *op, size_t es, int l, int q) {
+   size_t off = 0;
+   for (int k = 0; k < l; k++) off += (size_t)op->mg_ld[k] * (k == 0 ? 1 : 3);
+   return (char *)op->mg_buf + (off + (size_t)op->mg_ld[l] * q) * op->mg_cols * es;
+}
+/* the cycle at level l for the right-hand side b; the result goes to B[to] */
+static void mg_vcycle(mg_run *r, int l, const char *b, int64_t lb, char *const B[2], const int64_t LB[2], int to) {
+   primme_amd_operator *op = r->op;
+   double lo, hi;
+   int D;
+   mg_level_ends(op, l, &lo, &hi, &D);
+   if (l == op->mg_nlev - 1) { (void)mg_cheb(r, l, lo, hi, op->mg_cs, b, lb, B, LB, -1, to); return; }
+   const double slo = hi / (2.0 * D);
+   const int a = (to + op->mg_nu) % 2;             /* the pre-smoothed iterate: nu post-smoothing steps later it is in B[to] */
+   (void)mg_cheb(r, l, slo, hi, op->mg_nu, b, lb, B, LB, -1, a);
+   hipk_cheb_coef cf;                              /* the residual b - M y into the other panel */
+   memset(&cf, 0, sizeof(cf));
+   for (int c = 0; c < r->nc; c++) { cf.cx[c] = 1.0; cf.cy[c] = -op->mg_shift; cf.cw[c] = -op->mg_scale; }
+   mg_step(r, l, &cf, b, lb, B[a], LB[a], NULL, 0, B[1 - a], LB[1 - a]);
+   char *bc = mg_panel(op, r->es, l + 1, 0);
+   char *const Bc[2] = {mg_panel(op, r->es, l + 1, 1), mg_panel(op, r->es, l + 1, 2)};
+   const int64_t ldc = op->mg_ld[l + 1], LBc[2] = {ldc, ldc};
+   if (!r->rc) { r->rc = hipk_mg_restrict(r->stream, r->dt, op->mg_n[l], op->mg_n[l + 1], r->nc, B[1 - a], LB[1 - a], bc, ldc); g_mg_launches++; }
+   mg_vcycle(r, l + 1, bc, ldc, Bc, LBc, 0);
+   if (!r->rc) { r->rc = hipk_mg_prolong_add(r->stream, r->dt, op->mg_n[l], op->mg_n[l + 1], r->nc, Bc[0], ldc, B[a], LB[a]); g_mg_launches++; }
+   (void)mg_cheb(r, l, slo, hi, op->mg_nu, b, lb, B, LB, a, to);
+}
+
+extern "C" void primme_amd_multigrid_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
+      int *blockSize, struct primme_params *primme, int *ierr) {
+   primme_amd_operator *op = (primme_amd_operator *)primme->preconditioner;
+   void *stream = primme->queue ? (void *)*(hipStream_t *)primme->queue : NULL;
+   if (!op || op->mg_nlev < 1) { *ierr = 1; return; }
+   *ierr = 0;
+   if (*blockSize <= 0) return;
+   if (!stream) stream = hipk_ctx_stream(hipk_csr_ctx(op->A));
+   mg_run r;
+   r.op = op; r.stream = stream; r.dt = hipk_csr_dtype(op->A); r.es = op_elem(r.dt); r.rc = 0;
+   const int want = *blockSize < HIPK_CHEB_MAXCOLS ? *blockSize : HIPK_CHEB_MAXCOLS;
+   if (want > op->mg_cols) {                       /* scratch for the widest chunk seen */
+      if (op->mg_buf) (void)hipFree(op->mg_buf);
+      op->mg_buf = NULL; op->mg_cols = 0;
+      size_t elems = (size_t)op->mg_ld[0];
+      for (int l = 1; l < op->mg_nlev; l++) elems += 3 * (size_t)op->mg_ld[l];
+      if (hipMalloc(&op->mg_buf, elems * r.es * want) != hipSuccess) { *ierr = 1; return; }
+      op->mg_cols = want;
+   }
+   for (int c0 = 0; c0 < *blockSize && !r.rc; c0 += HIPK_CHEB_MAXCOLS) {
+      r.nc = *blockSize - c0 < HIPK_CHEB_MAXCOLS ? *blockSize - c0 : HIPK_CHEB_MAXCOLS;
+      const char *xc = (const char *)x + (size_t)c0 * *ldx * r.es;
+      char *const B[2] = {(char *)y + (size_t)c0 * *ldy * r.es, mg_panel(op, r.es, 0, 0)};
+      const int64_t LB[2] = {*ldy, op->mg_ld[0]};
+      g_mg_applies += r.nc;
+      mg_vcycle(&r, 0, xc, *ldx, B, LB, 0);
+   }
+   if (r.rc) *ierr = 1;
 }
 
 extern "C" int primme_amd_operator_set_complex(primme_amd_operator *op, int on) {

@@ -7,6 +7,7 @@
  *   primme_amd_csr_transpose      explicit A' for the singular value operator
  *   primme_amd_csr_complex_to_real  Hermitian matrix -> symmetric real-equivalent form
  *   primme_amd_csr_tile_plan      the row tiles, column windows and 16-bit index stream of the device CSR operator
+ *   primme_amd_mg_plan            the grids and weights of the geometric multigrid preconditioner (primme_amd.h)
  *
  * Indices are 0-based int32 (the device kernels' format); values are double, complex as
  * (re, im) pairs.  Everything returned is malloc'ed; release with primme_amd_host_free. */
@@ -16,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "primme_amd_io.h"
+#include "primme_amd.h"
 
 void primme_amd_host_free(void *p) { free(p); }
 
@@ -431,5 +433,36 @@ int primme_amd_csr_tile_plan(int64_t nrows, int64_t row0, int64_t x0, int64_t xl
    }
    free(tmax);
    *out = P;
+   return 0;
+}
+
+/* The levels of the geometric multigrid preconditioner (primme_amd_multigrid_precond).  Level 0 is the
+ * caller's grid with weights 1.  From a level to the next every dimension of 3 or more points is halved (n / 2: coarse point j
+ * sits on fine point 2 j + 1) and its weight, the factor of its 1-D Laplacian in the level operator, divided by 4; shorter
+ * dimensions are kept.  The last level is the first without a dimension of 3 or more points, or with at most
+ * PRIMME_AMD_MG_COARSE_POINTS points, or the PRIMME_AMD_MG_MAXLEVELS-th.  n and w hold PRIMME_AMD_MG_MAXLEVELS rows; the rows
+ * behind *nlevels are left alone.  Returns 0, -1 for a dimension below 1 or more than INT32_MAX points. */
+int primme_amd_mg_plan(const int dims[3], int *nlevels, int n[][3], double w[][3]) {
+   if (!dims || !nlevels || !n || !w) return -1;
+   int64_t pts = 1;
+   for (int d = 0; d < 3; d++) {
+      if (dims[d] < 1) return -1;
+      pts *= dims[d];
+      if (pts > INT32_MAX) return -1;
+      n[0][d] = dims[d]; w[0][d] = 1.0;
+   }
+   int l = 0;
+   while (l + 1 < PRIMME_AMD_MG_MAXLEVELS && pts > PRIMME_AMD_MG_COARSE_POINTS &&
+          (n[l][0] >= 3 || n[l][1] >= 3 || n[l][2] >= 3)) {
+      pts = 1;
+      for (int d = 0; d < 3; d++) {
+         const int c = n[l][d] >= 3;
+         n[l + 1][d] = c ? n[l][d] / 2 : n[l][d];
+         w[l + 1][d] = c ? w[l][d] / 4.0 : w[l][d];
+         pts *= n[l + 1][d];
+      }
+      l++;
+   }
+   *nlevels = l + 1;
    return 0;
 }
