@@ -109,7 +109,12 @@ int hipk_panel_dots(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const hipk_seg *seg
  * coef: DEVICE array of accumulator scalars, ldcoef rows stride.  nrm2 (DEVICE,
  * nx doubles) may be NULL.  One fused pass over the basis: the CGS update
  * (reference ortho.c:262-291: two Num_gemv_dhd + Num_dot) and the projector of
- * ortho_single_iteration (ortho.c:894-925). */
+ * ortho_single_iteration (ortho.c:894-925).
+ * Complex panels: the coefficients of one launch are staged on-chip, HIPK_Z_PROJECT_MAXCOEF of them.  With more
+ * basis columns than fit four right-hand columns at a time the launches take two or one column each; with more than
+ * HIPK_Z_PROJECT_MAXCOEF basis columns in all, hipk_panel_project and hipk_panel_project_to return -1 and write
+ * nothing. */
+#define HIPK_Z_PROJECT_MAXCOEF 2048
 int hipk_panel_project(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const hipk_seg *segs, int nseg,
       const double *coef_dev, int ldcoef, void *X, int64_t ldX, int nx, double *nrm2_dev);
 
@@ -122,8 +127,10 @@ int hipk_panel_project_to(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const hipk_se
 
 /* X <- (X - [segs] * coef) * M with M an nx x nx matrix (DEVICE, leading dimension nx), nx <= 8, in one
  * pass over X and the basis: the whole device step of a CholQR / SVQB sweep (reference
- * Num_ortho_kernel, ortho.c:963-1072).  Returns 1 if the shape is not covered (nx > 8): the caller
- * then uses hipk_panel_project + hipk_ritz_update. */
+ * Num_ortho_kernel, ortho.c:963-1072).  Returns 1, with nothing launched or written, if the shape is not
+ * covered: nx > 8, or, on complex panels, (basis columns) x (nx rounded up to 1, 2, 4 or 8) exceeds
+ * HIPK_Z_PROJECT_MAXCOEF (all nx columns go through one launch, M couples them: more than 256 basis + locked
+ * columns at nx = 5..8, 512 at 3..4, 1024 at 2).  The caller then uses hipk_panel_project + hipk_ritz_update. */
 int hipk_panel_project_mul(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const hipk_seg *segs, int nseg,
       const double *coef_dev, int ldcoef, const double *M_dev, void *X, int64_t ldX, int nx);
 

@@ -65,7 +65,10 @@ void hipk_cpu_counts(long *out, int reset) { for (int i = 0; i < 8; i++) { out[i
 int hipk_ctx_destroy(hipk_ctx *ctx) { if (getenv("HIPK_CPU_COUNTS")) fprintf(stderr, "hipk_cpu calls: dots %ld project %ld ritz %ld ritz_cgs %ld scale %ld\n", g_cnt[0], g_cnt[1], g_cnt[2], g_cnt[3], g_cnt[4]); free(ctx); return 0; }
 void *hipk_ctx_stream(hipk_ctx *ctx) { (void)ctx; return NULL; }
 int hipk_malloc(hipk_ctx *c, size_t b, void **p) { (void)c; *p = calloc(1, b ? b : 8); return *p ? 0 : -2; }
-int hipk_free(hipk_ctx *c, void *p) { (void)c; free(p); return 0; }
+static double *g_mirror_dev, *g_mirror_host; static size_t g_mirror_n;
+/* the mirror is one per process here (per context in the product): freeing the mirrored range ends it, or the results of
+ * a LATER context that happen to lie in the freed range would be copied into the freed host array */
+int hipk_free(hipk_ctx *c, void *p) { (void)c; if (p && p == (void *)g_mirror_dev) { g_mirror_dev = g_mirror_host = NULL; g_mirror_n = 0; } free(p); return 0; }
 int hipk_host_alloc(hipk_ctx *c, size_t b, void **p) { return hipk_malloc(c, b, p); }
 int hipk_host_free(hipk_ctx *c, void *p) { return hipk_free(c, p); }
 int hipk_h2d(hipk_ctx *c, void *d, const void *s, size_t b) { (void)c; memmove(d, s, b); return 0; }
@@ -73,7 +76,6 @@ int hipk_d2h(hipk_ctx *c, void *d, const void *s, size_t b) { (void)c; memmove(d
 int hipk_d2d(hipk_ctx *c, void *d, const void *s, size_t b) { (void)c; memmove(d, s, b); return 0; }
 int hipk_memset0(hipk_ctx *c, void *d, size_t b) { (void)c; memset(d, 0, b); return 0; }
 int hipk_sync(hipk_ctx *c) { (void)c; return 0; }
-static double *g_mirror_dev, *g_mirror_host; static size_t g_mirror_n;
 int hipk_ctx_set_mirror(hipk_ctx *c, double *d, double *h, size_t n) { (void)c; g_mirror_dev = d; g_mirror_host = h; g_mirror_n = n; return 0; }
 /* the checker's stand-in for the cross-rank second stage of the product's reductions (hipk_finalize_kernel<., XR>): when the stand-in
  * communicator of oracle/hostcheck_glue.c installs this hook, the results of a reduction pass through it (it sums them over the ranks

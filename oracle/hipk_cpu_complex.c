@@ -59,6 +59,7 @@ int hipk_z_panel_project_to(hipk_dtype dt, int64_t m, const hipk_seg *segs, int 
       const void *X, int64_t ldX, void *Xout, int64_t ldXout, int nx, double *nrm2) {
    const zc *coef = (const zc *)coef_;
    const int tot = zseg_total(segs, nseg);
+   if (nx > 0 && tot > HIPK_Z_PROJECT_MAXCOEF) return -1;      /* as the header says for complex panels */
    for (int c = 0; c < nx; c++) {
       const void *x = zcol(dt, X, ldX, c);
       void *o = (void *)zcol(dt, Xout, ldXout, c);
@@ -78,8 +79,10 @@ int hipk_z_panel_project_mul(hipk_dtype dt, int64_t m, const hipk_seg *segs, int
       const double *M_, void *X, int64_t ldX, int nx) {
    const zc *coef = (const zc *)coef_, *M = (const zc *)M_;
    if (nx <= 0) return 0;
-   if (nx > 8) return 1;
    const int tot = zseg_total(segs, nseg);
+   /* the return codes of the header: 1 = shape not covered (nx > 8, or the coefficients of the nx columns, rounded up to
+    * 1, 2, 4 or 8, exceed HIPK_Z_PROJECT_MAXCOEF) */
+   if (nx > 8 || (int64_t)tot * (nx <= 1 ? 1 : nx <= 2 ? 2 : nx <= 4 ? 4 : 8) > HIPK_Z_PROJECT_MAXCOEF) return 1;
    for (int64_t i = 0; i < m; i++) {
       zc xv[8], out[8];
       for (int c = 0; c < nx; c++) {

@@ -298,7 +298,7 @@ static int zpanel_dots_t(hipk_ctx *ctx, int64_t m, const ZSegs &sa, const void *
 
 /* ============================ NN panel: X -= [segs] coef (x M), |.|^2 =================================
  * coefficients (and M) staged in LDS; a lane streams the basis columns of its row once and updates NX values. */
-#define ZPROJ_LDS 2048      /* complex coefficients per launch: tot * NX <= this (32 KB + the column pointers) */
+#define ZPROJ_LDS HIPK_Z_PROJECT_MAXCOEF      /* 2048 complex coefficients per launch: tot * NX <= this (32 KB + the column pointers) */
 template <typename R, int NX, bool MUL>
 __global__ void __launch_bounds__(HIPK_BLOCK)
 zproject_kernel(ZSegs sa, const zacc *__restrict__ coef, int ldcoef, const zacc *__restrict__ M, const cpx<R> *X, int64_t ldX,
@@ -367,14 +367,18 @@ static int zproject_t(hipk_ctx *ctx, int64_t m, const ZSegs &sa, const double *c
    const int tot = sa.total;
    const int gx = zgrid(ctx, m, 4);
    const bool mul = M != NULL;
-   if (mul && nx > 8) return 1;
+   /* shapes one launch cannot stage, decided before anything is reserved or launched: the fused form takes all nx columns at
+    * once (its M couples them), so it reports "not covered" (1) and the caller takes the two-launch path; the plain form
+    * narrows its column chunk down to one and fails (-1) only beyond ZPROJ_LDS basis columns */
+   const int nxm = nx <= 1 ? 1 : nx <= 2 ? 2 : nx <= 4 ? 4 : 8;
+   if (mul && (nx > 8 || (size_t)tot * nxm > ZPROJ_LDS)) return 1;
+   if (!mul && tot > ZPROJ_LDS) return -1;
    if (nrm2_dev && hipk_reserve_partials(ctx, (size_t)nx * gx)) return -2;
    const int pslot = hipk_prof_begin(HIPK_PROF_PROJECT, ctx->stream, (double)(tot + 2 * nx) * (double)m * 2.0 * sizeof(R));
    for (int c0 = 0; c0 < nx;) {
       const int nc = nx - c0;
-      int NXV = mul ? (nx <= 1 ? 1 : nx <= 2 ? 2 : nx <= 4 ? 4 : 8) : (nc >= 4 ? 4 : nc >= 2 ? 2 : 1);
+      int NXV = mul ? nxm : (nc >= 4 ? 4 : nc >= 2 ? 2 : 1);
       while (!mul && NXV > 1 && (size_t)tot * NXV > ZPROJ_LDS) NXV >>= 1;
-      if ((size_t)tot * NXV > ZPROJ_LDS) return -1;
       const size_t lds = ((size_t)tot * NXV + (mul ? NXV * NXV : 0)) * sizeof(zacc) + (size_t)tot * sizeof(void *);
 #define ZP(NV, MV) hipLaunchKernelGGL((zproject_kernel<R, NV, MV>), dim3(gx), dim3(HIPK_BLOCK), lds, ctx->stream, sa, (const zacc *)coef, ldcoef, \
             (const zacc *)M, (const cpx<R> *)X, ldX, (cpx<R> *)Xout, ldXout, nx, c0, m, tot, nrm2_dev ? ctx->partials : (double *)NULL)
@@ -605,7 +609,9 @@ static int zritz_launch(hipk_ctx *ctx, int64_t m, const void *V, const void *W, 
 #define ZR2(LV, A, B, C, G) do { ZJobsL<LV> jl; if (!launched && zjobs_split<LV>(jobs, nj, A, B, C, jl)) { \
             hipLaunchKernelGGL((zritz2_kernel<R, LV, A, B, C>), dim3(G), dim3(HIPK_BLOCK), 0, ctx->stream, (const cpx<R> *)V, (const cpx<R> *)W, ld, k, \
                   (const zacc *)h, ldh, theta, jl, m, norms ? ctx->partials : (double *)NULL); launched = G; } } while (0)
-      if (nr <= 4) { ZR2(2, 7, 7, 2, g2); ZR2(2, 9, 7, 2, g2); ZR2(2, 12, 10, 2, g2); ZR2(4, 6, 5, 1, g4); ZR2(4, 8, 7, 1, g4); }
+      /* (a four-lane <6, 5, 1> stood between <12, 10, 2> and <8, 7, 1>: it holds 24 + 20 + 4 jobs, exactly what the two-lane
+       * <12, 10, 2> tried before it holds, so no job list ever reached it) */
+      if (nr <= 4) { ZR2(2, 7, 7, 2, g2); ZR2(2, 9, 7, 2, g2); ZR2(2, 12, 10, 2, g2); ZR2(4, 8, 7, 1, g4); }
       ZR2(2, 4, 4, 8, g2); ZR2(4, 8, 4, 4, g4);
 #undef ZR2
       if (launched) {

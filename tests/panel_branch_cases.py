@@ -67,6 +67,8 @@ class Operand:
         self.off = GUARD + shift
         n = self.off + max(ncols, 1) * self.ld + GUARD
         self.host = np.full(n, np.nan, self.dtype)
+        if self.dtype.kind == "c":
+            self.host.imag = np.nan                  # a complex element is NaN in both halves
         self.written = np.zeros(n, bool)
 
     def index(self, cols, rows=None):
@@ -562,6 +564,13 @@ def coverage(table):
 # ------------------------------------------------------------------------------------------------------------------
 # runners: one case on one side (kernel_harness.Dev or Host)
 # ------------------------------------------------------------------------------------------------------------------
+def _bits(a):
+    """one row of integers per element (two for a complex element: either half differing counts)"""
+    a = np.ascontiguousarray(a).reshape(-1)
+    parts = 2 if a.dtype.kind == "c" else 1
+    return a.view(np.uint64 if a.dtype.itemsize // parts == 8 else np.uint32).reshape(a.size, parts)
+
+
 class Report:
     """worst error-to-bound ratio and the list of failures of a group of cases"""
 
@@ -582,14 +591,12 @@ class Report:
             self.fails.append(f"{what}: error/bound = {w:.3g} at flat index {int(np.argmax(ratio))}")
 
     def same_bits(self, what, a, b):
-        iv = np.uint64 if a.dtype.itemsize == 8 else np.uint32
-        bad = np.flatnonzero(a.view(iv) != b.view(iv))
+        bad = np.flatnonzero((_bits(a) != _bits(b)).any(axis=1))
         if bad.size:
             self.fails.append(f"{what}: {bad.size} elements differ bit-wise, first at {int(bad[0])}")
 
     def guard(self, what, op, after):
-        iv = np.uint64 if op.dtype.itemsize == 8 else np.uint32
-        bad = np.flatnonzero((op.host.view(iv) != after.view(iv)) & ~op.written)
+        bad = np.flatnonzero((_bits(op.host) != _bits(after)).any(axis=1) & ~op.written)
         if bad.size:
             e = int(bad[0]) - op.off
             self.fails.append(f"{what}: {bad.size} guard/padding/input elements changed, first at column {e // op.ld} row {e % op.ld} "
@@ -868,13 +875,14 @@ _RUN = {"residual": _run_residual, "residual_dev": lambda s, c, r: _run_residual
         "triple": _run_triple}
 
 
-def run_cases(side_factory, cases):
-    """all cases on ONE side object; returns the Report (the caller asserts on .fails and prints .summary())"""
+def run_cases(side_factory, cases, runners=None):
+    """all cases on ONE side object; returns the Report (the caller asserts on .fails and prints .summary()).
+    runners: the table {entry point: runner} of another case module (tests/complex_branch_cases.py)"""
     rep = Report()
     side = side_factory()
     try:
         for c in cases:
-            _RUN[c["ep"]](side, c, rep)
+            (runners or _RUN)[c["ep"]](side, c, rep)
             rep.ncases += 1
             if hasattr(side, "keep") and len(side.keep) > 64:
                 _release(side)
