@@ -343,6 +343,35 @@ int primme_amd_operator_set_multigrid(struct primme_amd_operator *op, int nx, in
 void primme_amd_multigrid_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
       int *blockSize, struct primme_params *primme, int *ierr);
 void primme_amd_multigrid_stats(long *applies, long *launches);
+/* Aggregation algebraic multigrid preconditioner for CSR operators (no reference counterpart): y = K^-1 x
+ * is ONE symmetric V(smooth_steps, smooth_steps) cycle from a zero start for M = A + shift I, A the operator's own SYMMETRIC
+ * CSR matrix (a positive diagonal; symmetry is the caller's promise), shift >= 0.  The hierarchy is built on the host from the
+ * CSR arrays handed over (the ones the operator was created from, values in the operator's dtype) by plain aggregation
+ * (primme_amd_amg_plan_create in primme_amd_io.h: strength threshold theta, Galerkin coarse matrices), uploaded, and the host
+ * copy freed.  K does not follow the solver's shifts and is symmetric positive definite: GD+k, JDQMR and the generalised
+ * problems take it.
+ *    primme_amd_operator_set_amg(op, rowptr_host, colind_host, values_host, smooth_steps, coarse_steps, theta, over, shift)
+ *    (usual values 2, 16, 0.08, 1.0, 0.0), then primme->preconditioner = the operator handle and
+ *    primme->applyPreconditioner = primme_amd_amg_precond.
+ * Every level but the last: smooth_steps steps of the Chebyshev iteration for D_l^-1 M_l on [rho_l / 4, rho_l] from zero, the
+ * residual, its restriction (sums over the aggregates), the coarse cycle, y += over P y_c (over in [1, 2): the over-correction
+ * of unsmoothed aggregation; 1 is the textbook cycle), and the same polynomial again from the corrected iterate.  Last level:
+ * at most PRIMME_AMD_AMG_DENSE_ROWS rows: the dense inverse from a host Cholesky factorisation, one launch; more (the
+ * aggregation stalled): coarse_steps Chebyshev steps on [rho_L / 4, rho_L].  Level 0 runs on the operator's own matrix with the
+ * shift folded into the product; the other levels are hipk_csr_create handles.  Kernels: csrc/hipk_amg.hip.
+ * set_amg returns -44 for a row-partitioned operator, a complex operator, the real-equivalent mode or a stencil operator (that
+ * one has set_multigrid); -1 for steps < 1, theta outside [0, 1), over outside [1, 2), shift < 0, host arrays whose size
+ * differs from the operator's, a plan error (a row without a positive diagonal entry) or a last level that is not positive
+ * definite; the operator is then unchanged.  The scratch (4 vectors per level and column of the block, at most 8 columns) is
+ * allocated at the first application and freed with the operator; block columns beyond 8 are processed in chunks.  The
+ * products inside are not counted in numMatvecs.
+ * primme_amd_amg_stats: for this process since the last call, the vectors preconditioned, the launches (kernels and level
+ * products) and the levels of the hierarchy applied last. */
+int primme_amd_operator_set_amg(struct primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smooth_steps, int coarse_steps, double theta, double over, double shift);
+void primme_amd_amg_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
+      int *blockSize, struct primme_params *primme, int *ierr);
+void primme_amd_amg_stats(long *applies, long *launches, long *levels);
 /* globalSumReal over RCCL: set primme->commInfo = handle from primme_amd_comm_create().
  * When the solver sees this exact function installed it reduces its DEVICE partials
  * with ncclAllReduce before the (single) device->host copy; called directly it also

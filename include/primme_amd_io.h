@@ -104,6 +104,43 @@ typedef struct primme_amd_tile_plan {
 int primme_amd_csr_tile_plan(int64_t nrows, int64_t row0, int64_t x0, int64_t xlen, int64_t ncols_global, const int32_t *rowptr,
       const int32_t *colind, const void *values, size_t elem_size, int real_values, primme_amd_tile_plan **P);
 void primme_amd_tile_plan_free(primme_amd_tile_plan *P);
+/* Hierarchy of the aggregation algebraic multigrid preconditioner (primme_amd_amg_precond in primme_amd.h; DESIGN.md
+ * section 4o), built on the host from the CSR arrays of a SYMMETRIC matrix A with a positive diagonal: symmetry is the caller's
+ * promise and is not checked.  values: elem_size 8 (double) or 4 (float).  Level 0 is M_0 = A + shift I; level l + 1 is the
+ * Galerkin matrix M_{l+1} = P_l' M_l P_l of plain (unsmoothed) aggregation, P_l the 0/1 matrix of agg_l, summed in double with
+ * sorted columns and one entry per position.
+ *   strong   i ~ j (i != j) when |m_ij| >= theta sqrt(m_ii m_jj)
+ *   pass 1   rows in index order: a free row whose strong neighbours are all free founds an aggregate with them
+ *   pass 2   rows in index order: a free row joins the pass-1 aggregate it has the largest strong |m_ij| to (ties: the lowest
+ *            aggregate number); rows that joined in this pass attract nobody
+ *   pass 3   rows in index order: a row still free founds an aggregate with its free strong neighbours (maybe alone)
+ * The result depends on the matrix alone.  Level l is the last when n_l <= PRIMME_AMD_AMG_DENSE_ROWS, when it is level
+ * PRIMME_AMD_AMG_MAXLEVELS - 1, or when the aggregation would keep more than 0.8 n_l rows (the aggregation is then discarded).
+ * Per level: n rows, the CSR arrays of M_l, dinv = 1 / diag(M_l), rho = max_i sum_j |m_ij| / m_ii (a bound on the spectrum
+ * of D^-1 M_l) and, but on the last level (nc = 0, NULL), the aggregate map agg[n] with values in [0, nc) and its inverse:
+ * aggregate j holds the rows aggrows[aggptr[j] .. aggptr[j + 1]), ascending.
+ * primme_amd_amg_plan_create returns 0 and *plan (release with primme_amd_amg_plan_free), -1 for n < 1, theta outside [0, 1),
+ * shift < 0, a row without a diagonal entry or a diagonal entry <= 0 on any level, -4 beyond int32, -5 out of memory.
+ * primme_amd_amg_coarse_inverse writes G = M_L^-1 (n_L x n_L, symmetric, n_L <= PRIMME_AMD_AMG_DENSE_ROWS) of the last
+ * level from a Cholesky factorisation; -1 when M_L is not positive definite or has more rows. */
+#define PRIMME_AMD_AMG_MAXLEVELS 24
+#define PRIMME_AMD_AMG_DENSE_ROWS 256
+typedef struct primme_amd_amg_level {
+   int64_t n, nnz, nc;
+   int32_t *rowptr, *colind;
+   double *values, *dinv;
+   double rho;
+   int32_t *agg, *aggptr, *aggrows;
+} primme_amd_amg_level;
+typedef struct primme_amd_amg_plan {
+   int nlevels;
+   double shift, theta;
+   primme_amd_amg_level level[PRIMME_AMD_AMG_MAXLEVELS];
+} primme_amd_amg_plan;
+int primme_amd_amg_plan_create(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
+      double shift, double theta, primme_amd_amg_plan **plan);
+void primme_amd_amg_plan_free(primme_amd_amg_plan *plan);
+int primme_amd_amg_coarse_inverse(const primme_amd_amg_plan *plan, double *G);
 void primme_amd_host_free(void *p);
 #ifdef __cplusplus
 }

@@ -471,6 +471,35 @@ int hipk_mg_restrict(void *hip_stream, hipk_dtype dt, const int nf[3], const int
 int hipk_mg_prolong_add(void *hip_stream, hipk_dtype dt, const int nf[3], const int nc[3], int nx, const void *C, int64_t ldc,
       void *Y, int64_t ldy);
 
+/* ---- aggregation algebraic multigrid on a CSR hierarchy (csrc/hipk_amg.hip; primme_amd_amg_precond, no reference
+ * counterpart).  What a V-cycle does between the level products (hipk_csr_matvec), for panels of 1 .. HIPK_CHEB_MAXCOLS
+ * columns; HIPK_F64 / HIPK_F32 (complex: -44), the arithmetic in double.  Leading dimensions are free; an access moves 16
+ * bytes where every streamed panel is 16-byte aligned (base and leading dimension; dinv: its base), one element where not.  No
+ * atomics: every sum has one order and a result is the same from run to run.
+ *   hipk_amg_smooth_update  Out = cy Yk + cp Yprev + dinv o (cx X + cw W), m rows, coefficients per column; dinv (m doubles)
+ *                           NULL reads as 1; W, Yk and Yprev may each be NULL (the term is left out); row-local, so Out may
+ *                           be any input.  With W = M Yk a step of the Chebyshev iteration for D^-1 M; with dinv = NULL,
+ *                           cx = 1, cw = -1 the residual X - W
+ *   hipk_amg_restrict       C[j] = sum of F[i] over the rows i of aggregate j = aggrows[aggptr[j] .. aggptr[j + 1]), nc
+ *                           aggregates of nf rows.  At most 64 rows: added in ascending order by one lane; more: lane l of
+ *                           a wave adds the rows first + l, first + l + 64, ... and the 64 partial sums are folded by a
+ *                           fixed butterfly
+ *   hipk_amg_prolong_add    Y[i] += over C[agg[i]], nf rows
+ *   hipk_amg_dense_apply    Y = G X, G dense symmetric n x n in double, n <= PRIMME_AMD_AMG_DENSE_ROWS (primme_amd_io.h);
+ *                           one launch, element accesses (a column is at most 2 KB); Y may be X
+ * aggptr (nc + 1), aggrows (nf) and agg (nf) are DEVICE arrays of the library's own making (from primme_amd_amg_plan_create):
+ * the entry points check sizes and pointers and TRUST the indices — an index out of range is an access out of range.
+ * -1: argument error (rows < 1, nc > nf, more than HIPK_CHEB_MAXCOLS columns, a NULL panel that is needed, F == C, C == Y). */
+int hipk_amg_smooth_update(void *hip_stream, hipk_dtype dt, int64_t m, int nx, const hipk_cheb_coef *coef, const double *dinv,
+      const void *X, int64_t ldx, const void *W, int64_t ldw, const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp,
+      void *Out, int64_t ldo);
+int hipk_amg_restrict(void *hip_stream, hipk_dtype dt, int64_t nf, int64_t nc, const int32_t *aggptr, const int32_t *aggrows, int nx,
+      const void *F, int64_t ldf, void *C, int64_t ldc);
+int hipk_amg_prolong_add(void *hip_stream, hipk_dtype dt, int64_t nf, int64_t nc, const int32_t *agg, double over, int nx,
+      const void *C, int64_t ldc, void *Y, int64_t ldy);
+int hipk_amg_dense_apply(void *hip_stream, hipk_dtype dt, int n, const double *G, int nx, const void *X, int64_t ldx, void *Y,
+      int64_t ldy);
+
 /* ---- Rayleigh-Ritz small solve on the device (reference solve_projection.c:188-331 calls xHEEVX,
  * blaslapack.c:1024-1143).  Symmetric n x n (n <= 64), upper triangle of A_host referenced;
  * eigenvalues ascending in evals_host, orthonormal eigenvectors in Z_host.  One workgroup, parallel

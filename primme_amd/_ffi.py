@@ -339,6 +339,26 @@ def declare_multigrid(lib):
     lib.hipk_mg_prolong_add.restype = C.c_int
 
 
+def declare_amg(lib):
+    """The aggregation algebraic multigrid preconditioner (include/primme_amd.h) and its kernels (csrc/hipk_amg.hip): product
+    library only; the plan functions are host code that the CPU checker build has too (tests/amg_cases.py declares them there)."""
+    P = C.POINTER
+    lib.primme_amd_operator_set_amg.argtypes = [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double]
+    lib.primme_amd_operator_set_amg.restype = C.c_int
+    lib.primme_amd_amg_precond.argtypes = [_vp, P(PRIMME_INT), _vp, P(PRIMME_INT), P(_i), _vp, P(_i)]
+    lib.primme_amd_amg_precond.restype = None
+    lib.primme_amd_amg_stats.argtypes = [P(C.c_long), P(C.c_long), P(C.c_long)]
+    lib.primme_amd_amg_stats.restype = None
+    lib.hipk_amg_smooth_update.argtypes = [_vp, _i, _i64, _i, P(HipkChebCoef), _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]
+    lib.hipk_amg_smooth_update.restype = C.c_int
+    lib.hipk_amg_restrict.argtypes = [_vp, _i, _i64, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64]
+    lib.hipk_amg_restrict.restype = C.c_int
+    lib.hipk_amg_prolong_add.argtypes = [_vp, _i, _i64, _i64, _vp, C.c_double, _i, _vp, _i64, _vp, _i64]
+    lib.hipk_amg_prolong_add.restype = C.c_int
+    lib.hipk_amg_dense_apply.argtypes = [_vp, _i, _i, _vp, _i, _vp, _i64, _vp, _i64]
+    lib.hipk_amg_dense_apply.restype = C.c_int
+
+
 def declare_formats(lib):
     """Creation with options and the queries of the one-column product's form: product library only (the CPU checker has one form)."""
     P = C.POINTER
@@ -393,6 +413,7 @@ def load_product():
         declare_kernels(lib)
         declare_chebyshev(lib)
         declare_multigrid(lib)
+        declare_amg(lib)
         declare_formats(lib)
         _cache["product"] = lib
     return _cache["product"]

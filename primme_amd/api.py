@@ -67,7 +67,8 @@ class Result:
                                                        "locking", "orth", "aNorm", "eps", "initSize", "dynamicMethodSwitch")}
         self.params["maxPrevRetain"] = params.restartingParams.maxPrevRetain
         # Chebyshev preconditioner: {"applies", "operator_products", "fused_steps"} of this solve (counted in vectors);
-        # multigrid preconditioner: {"applies", "launches"} (vectors, kernel launches)
+        # multigrid preconditioner: {"applies", "launches"} (vectors, kernel launches); algebraic multigrid: {"applies",
+        # "launches", "levels"}
         self.precond_stats = None
 
 
@@ -225,6 +226,22 @@ class Session:
                 raise ValueError(f"precond={precond!r}: the multigrid preconditioner serves real operators")
             if self.comm is not None:
                 raise ValueError(f"precond={precond!r}: the multigrid preconditioner serves single-rank operators")
+        amg = isinstance(precond, (tuple, list)) and len(precond) > 0 and precond[0] == "amg"
+        if amg:
+            if not 1 <= len(precond) <= 6:
+                raise ValueError("precond: ('amg'[, smooth_steps[, coarse_steps[, theta[, over[, shift]]]]])")
+            if not (self.be.native_operator and hasattr(lib, "primme_amd_amg_precond")):
+                raise ValueError(f"precond={precond!r}: the algebraic multigrid preconditioner runs on the device operator of the "
+                                 f"product library; back end {self.backend!r} has no such operator")
+            if user_precond is not None:
+                raise ValueError("precond=('amg', ...) and user_precond exclude each other")
+            if self.cplx:
+                raise ValueError(f"precond={precond!r}: the algebraic multigrid preconditioner serves real operators")
+            if self.comm is not None:
+                raise ValueError(f"precond={precond!r}: the algebraic multigrid preconditioner serves single-rank operators")
+            if op.csr is None:
+                raise ValueError(f"precond={precond!r}: the algebraic multigrid preconditioner reads the CSR arrays of the operator; "
+                                 "a stencil operator has precond=('multigrid', dims)")
         p = F.PrimmeParams()
         nLocal = op.nrows
         v0 = None if v0 is None else np.asarray(v0, dtype=dtype).reshape(nLocal, -1)
@@ -317,6 +334,26 @@ class Session:
                 p.preconditioner = self.oph
                 p.applyPreconditioner = C.cast(lib.primme_amd_multigrid_precond, C.c_void_p)
                 p.correctionParams.precondition = 1
+            elif amg:
+                # ("amg"[, smooth_steps[, coarse_steps[, theta[, over[, shift]]]]]): one V-cycle for A + shift on the hierarchy
+                # that the library aggregates from the operator's own CSR arrays
+                nu = int(precond[1]) if len(precond) > 1 else 2
+                ncs = int(precond[2]) if len(precond) > 2 else 16
+                theta = float(precond[3]) if len(precond) > 3 else 0.08
+                over = float(precond[4]) if len(precond) > 4 else 1.0
+                shift = float(precond[5]) if len(precond) > 5 else 0.0
+                rp = np.ascontiguousarray(op.csr[0], dtype=np.int32)
+                ci = np.ascontiguousarray(op.csr[1], dtype=np.int32)
+                va = np.ascontiguousarray(op.csr[2], dtype=dtype)
+                rc = lib.primme_amd_operator_set_amg(self.oph, rp.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                                     va.ctypes.data_as(C.c_void_p), nu, ncs, theta, over, shift)
+                if rc:
+                    raise ValueError(f"precond={precond!r}: needs a real single-rank CSR operator ({rc}) with a positive diagonal, "
+                                     "steps >= 1, 0 <= theta < 1, 1 <= over < 2 and shift >= 0")
+                lib.primme_amd_amg_stats(None, None, None)              # the counters are per process: start this solve at zero
+                p.preconditioner = self.oph
+                p.applyPreconditioner = C.cast(lib.primme_amd_amg_precond, C.c_void_p)
+                p.correctionParams.precondition = 1
             elif precond is not None:
                 # "jacobi": per-vector shifts of the solver; ("jacobi", s): fixed K = diag(A) - s
                 if precond == "jacobi": lib.primme_amd_operator_set_jacobi(self.oph, 0, 0.0)
@@ -393,6 +430,10 @@ class Session:
             st = [C.c_long(0), C.c_long(0)]
             lib.primme_amd_multigrid_stats(*[C.byref(v) for v in st])
             res.precond_stats = dict(zip(("applies", "launches"), (v.value for v in st)))
+        if amg:
+            st = [C.c_long(0), C.c_long(0), C.c_long(0)]
+            lib.primme_amd_amg_stats(*[C.byref(v) for v in st])
+            res.precond_stats = dict(zip(("applies", "launches", "levels"), (v.value for v in st)))
         return res
 
 
@@ -407,6 +448,9 @@ def eigsh(op, backend="hip", comm=None, dtype=np.float64, complex_form="native",
     ("multigrid", dims[, smooth_steps[, coarse_steps[, scale[, shift]]]]): one geometric multigrid V-cycle for
     scale * Laplacian + shift on the grid dims = (nx[, ny[, nz]]), x fastest (defaults 2, 16, 1, 0), for grid Laplacians in any
     operator form and for -Laplacian + V with shift about the mean of V; Result.precond_stats = {"applies", "launches"}.
+    ("amg"[, smooth_steps[, coarse_steps[, theta[, over[, shift]]]]]): one aggregation algebraic multigrid V-cycle for A + shift
+    on a hierarchy built from the CSR arrays of the operator, a symmetric matrix with a positive diagonal (defaults 2, 16, 0.08,
+    1, 0): FEM, structural and graph matrices without a grid; Result.precond_stats = {"applies", "launches", "levels"}.
     members: {"name": value} set through primme_set_member after the method preset and before `tweak`, e.g.
     {"correctionParams.maxInnerIterations": 0, "projectionParams.projection": "primme_proj_refined"}; a string for an
     enum member is an enumerator name (primme_constant_info); an unknown member or enumerator is a ValueError.

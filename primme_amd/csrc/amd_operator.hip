@@ -8,6 +8,28 @@
 #include "primme_amd_comm.h"
 #include "comm_internal.h"
 #include "eigs_internal.h"   /* primme_amd_svds_operator_is_local */
+#include "primme_amd_io.h"     /* primme_amd_amg_plan */
+
+/* aggregation AMG preconditioner (primme_amd_amg_precond): the hierarchy on the device, nlev = 0 until configured.  Level l
+   has n rows, nc aggregates (0 on the last level), the operator M (level 0: NULL, the operator's own matrix serves with the
+   shift folded into the product), dinv = 1 / diag(M_l), the spectral bound rho and the aggregate maps; ld elements per scratch
+   column (16-byte columns).  G: the dense inverse of the last level when it has at most PRIMME_AMD_AMG_DENSE_ROWS rows.
+   buf: ONE allocation of cols columns per panel, level 0 an iterate and the product, every other level the right-hand side,
+   two iterates and the product */
+struct amg_level_dev {
+   int64_t n, nc, ld;
+   double rho;
+   hipk_csr *M;
+   double *dinv;
+   int32_t *agg, *aggptr, *aggrows;
+};
+struct amg_state {
+   int nlev, nu, cs, cols;
+   double over, shift;
+   amg_level_dev lv[PRIMME_AMD_AMG_MAXLEVELS];
+   double *G;
+   void *buf;
+};
 
 struct primme_amd_operator {
    hipk_csr *A;
@@ -41,7 +63,9 @@ struct primme_amd_operator {
    double mg_w[PRIMME_AMD_MG_MAXLEVELS][3];
    int64_t mg_ld[PRIMME_AMD_MG_MAXLEVELS];
    void *mg_buf;
+   amg_state amg;
 };
+static void amg_release(amg_state *s);
 
 static size_t op_elem(hipk_dtype dt) { return dt == HIPK_F64 ? 8 : dt == HIPK_F32 ? 4 : dt == HIPK_C64 ? 16 : 8; }
 
@@ -100,6 +124,7 @@ extern "C" int primme_amd_operator_destroy(primme_amd_operator *op) {
    if (op->cheb_y) (void)hipFree(op->cheb_y);
    if (op->cheb_w) (void)hipFree(op->cheb_w);
    if (op->mg_buf) (void)hipFree(op->mg_buf);
+   amg_release(&op->amg);
    free(op);
    return 0;
 }
@@ -545,6 +570,221 @@ extern "C" void primme_amd_multigrid_precond(void *x, PRIMME_INT *ldx, void *y, 
       const int64_t LB[2] = {*ldy, op->mg_ld[0]};
       g_mg_applies += r.nc;
       mg_vcycle(&r, 0, xc, *ldx, B, LB, 0);
+   }
+   if (r.rc) *ierr = 1;
+}
+
+/* ---- aggregation algebraic multigrid preconditioner for CSR operators (kernels in hipk_amg.hip) ----------
+ * y = K^-1 x: one symmetric V(nu, nu) cycle from zero for M = A + shift I on the hierarchy of primme_amd_amg_plan_create,
+ *    vcycle(l, b):  l == last: G b (at most PRIMME_AMD_AMG_DENSE_ROWS rows) or nu_c Chebyshev steps from zero
+ *                   y = nu Chebyshev steps from zero;  y += over P vcycle(l + 1, P' (b - M_l y));  nu Chebyshev steps from y
+ * The Chebyshev iteration is the one for D_l^-1 M_l on [rho_l / 4, rho_l]: y_1 = D^-1 b / tb, then
+ *    y_{k+1} = y_k + a (y_k - y_{k-1}) + bb D^-1 (b - M y_k),  a = rho_{k+1} rho_k, bb = 2 rho_{k+1} / dl,
+ * and started at y: y_1 = y + D^-1 (b - M y) / tb, which returns y + p(D^-1 M) D^-1 (b - M y) with the smoother's own
+ * polynomial p and makes K symmetric (the construction of 4n).  A step is the level product (hipk_csr_matvec; level 0 the
+ * operator's own matrix, hipk_csr_matvec_shifted adding the shift) and one hipk_amg_smooth_update.  The iterates of a level
+ * alternate between two panels, y_{k+1} over y_{k-1}; a sequence starts in the panel that makes its last iterate land where
+ * the next stage expects it (the result of a level in panel 0; level 0: the caller's y). */
+static long g_amg_applies, g_amg_launches, g_amg_levels;
+extern "C" void primme_amd_amg_stats(long *applies, long *launches, long *levels) {
+   if (applies) *applies = g_amg_applies;
+   if (launches) *launches = g_amg_launches;
+   if (levels) *levels = g_amg_levels;             /* of the hierarchy applied last */
+   g_amg_applies = g_amg_launches = g_amg_levels = 0;
+}
+
+static void amg_release(amg_state *s) {
+   for (int l = 0; l < PRIMME_AMD_AMG_MAXLEVELS; l++) {
+      amg_level_dev *L = &s->lv[l];
+      if (L->M) (void)hipk_csr_destroy(L->M);
+      if (L->dinv) (void)hipFree(L->dinv);
+      if (L->agg) (void)hipFree(L->agg);
+      if (L->aggptr) (void)hipFree(L->aggptr);
+      if (L->aggrows) (void)hipFree(L->aggrows);
+   }
+   if (s->G) (void)hipFree(s->G);
+   if (s->buf) (void)hipFree(s->buf);
+   memset(s, 0, sizeof(*s));
+}
+/* a device copy of `bytes` host bytes; 0 on success */
+static int amg_to_device(hipk_ctx *ctx, void **dst, const void *src, size_t bytes) {
+   if (hipMalloc(dst, bytes ? bytes : 1) != hipSuccess) { *dst = NULL; return -2; }
+   return bytes ? hipk_upload(ctx, *dst, src, bytes) : 0;
+}
+
+extern "C" int primme_amd_operator_set_amg(primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smooth_steps, int coarse_steps, double theta, double over, double shift) {
+   if (!op) return -1;
+   const hipk_dtype dt = hipk_csr_dtype(op->A);
+   if (op->mode != 0 || (op->comm && primme_amd_comm_size(op->comm) > 1) || op->ldscale != 1 || (dt != HIPK_F64 && dt != HIPK_F32)) return -44;
+   if (hipk_csr_kind(op->A) != 0 || op->lo > 0 || op->hi > 0) return -44;          /* a stencil has ("multigrid", ...) */
+   if (!rowptr_host || !colind_host || !values_host || smooth_steps < 1 || coarse_steps < 1 || !(theta >= 0.0 && theta < 1.0) ||
+       !(over >= 1.0 && over < 2.0) || !(shift >= 0.0)) return -1;
+   const int64_t n = hipk_csr_nrows(op->A);
+   if (n < 1 || rowptr_host[0] != 0 || (int64_t)rowptr_host[n] != hipk_csr_nnz(op->A)) return -1;
+   primme_amd_amg_plan *P = NULL;
+   if (primme_amd_amg_plan_create(n, rowptr_host, colind_host, values_host, dt == HIPK_F64 ? 8 : 4, shift, theta, &P)) return -1;
+   hipk_ctx *ctx = hipk_csr_ctx(op->A);
+   amg_state s;
+   memset(&s, 0, sizeof(s));
+   s.nlev = P->nlevels; s.nu = smooth_steps; s.cs = coarse_steps; s.over = over; s.shift = shift;
+   int rc = 0;
+   for (int l = 0; l < P->nlevels && !rc; l++) {
+      const primme_amd_amg_level *H = &P->level[l];
+      amg_level_dev *L = &s.lv[l];
+      L->n = H->n; L->nc = H->nc; L->rho = H->rho; L->ld = (H->n + 3) / 4 * 4;
+      rc = amg_to_device(ctx, (void **)&L->dinv, H->dinv, sizeof(double) * (size_t)H->n);
+      if (!rc && l > 0) {
+         if (dt == HIPK_F64) rc = hipk_csr_create(ctx, dt, H->n, H->n, 0, H->rowptr, H->colind, H->values, &L->M);
+         else {
+            float *vf = (float *)malloc(sizeof(float) * (size_t)(H->nnz > 0 ? H->nnz : 1));
+            if (!vf) rc = -2;
+            for (int64_t q = 0; q < H->nnz && !rc; q++) vf[q] = (float)H->values[q];
+            if (!rc) rc = hipk_csr_create(ctx, dt, H->n, H->n, 0, H->rowptr, H->colind, vf, &L->M);
+            free(vf);
+         }
+      }
+      if (!rc && H->nc > 0) {
+         rc = amg_to_device(ctx, (void **)&L->agg, H->agg, sizeof(int32_t) * (size_t)H->n);
+         if (!rc) rc = amg_to_device(ctx, (void **)&L->aggptr, H->aggptr, sizeof(int32_t) * (size_t)(H->nc + 1));
+         if (!rc) rc = amg_to_device(ctx, (void **)&L->aggrows, H->aggrows, sizeof(int32_t) * (size_t)H->n);
+      }
+   }
+   const int64_t nl = P->level[P->nlevels - 1].n;
+   if (!rc && nl <= PRIMME_AMD_AMG_DENSE_ROWS) {
+      double *G = (double *)malloc(sizeof(double) * (size_t)(nl * nl));
+      rc = G ? primme_amd_amg_coarse_inverse(P, G) : -2;             /* -1: the matrix is not positive definite */
+      if (!rc) rc = amg_to_device(ctx, (void **)&s.G, G, sizeof(double) * (size_t)(nl * nl));
+      free(G);
+   }
+   primme_amd_amg_plan_free(P);
+   if (rc) { amg_release(&s); return -1; }
+   amg_release(&op->amg);                           /* the operator changes only when everything is in order */
+   op->amg = s;
+   return 0;
+}
+
+struct amg_run {
+   primme_amd_operator *op;
+   void *stream;
+   hipk_dtype dt;
+   size_t es;
+   int nc;
+   int rc;
+};
+/* W = M_l Y */
+static void amg_product(amg_run *r, int l, const char *y, int64_t ldy, char *w, int64_t ldw) {
+   if (r->rc) return;
+   amg_state *s = &r->op->amg;
+   if (l > 0) r->rc = hipk_csr_matvec(s->lv[l].M, r->stream, y, ldy, w, ldw, r->nc);
+   else if (s->shift == 0.0) r->rc = hipk_csr_matvec(r->op->A, r->stream, y, ldy, w, ldw, r->nc);
+   else {
+      double ms[HIPK_CHEB_MAXCOLS];
+      for (int c = 0; c < r->nc; c++) ms[c] = -s->shift;
+      r->rc = hipk_csr_matvec_shifted(r->op->A, r->stream, y, ldy, w, ldw, r->nc, ms);
+   }
+   g_amg_launches++;
+}
+static void amg_update(amg_run *r, int l, const hipk_cheb_coef *cf, int with_dinv, const char *x, int64_t ldx, const char *w, int64_t ldw,
+      const char *yk, int64_t ldk, const char *yp, int64_t ldp, char *out, int64_t ldo) {
+   if (r->rc) return;
+   const amg_level_dev *L = &r->op->amg.lv[l];
+   r->rc = hipk_amg_smooth_update(r->stream, r->dt, L->n, r->nc, cf, with_dinv ? L->dinv : NULL, x, ldx, w, ldw, yk, ldk, yp, ldp, out, ldo);
+   g_amg_launches++;
+}
+/* `steps` steps of the Chebyshev iteration for D^-1 M_l y = D^-1 b on [rho_l / 4, rho_l] with the iterates in Y[0], Y[1] and the
+ * product in W: from zero when from < 0 (the result in Y[to]), else from Y[from].  Returns the panel of the last iterate. */
+static int amg_cheb(amg_run *r, int l, int steps, const char *b, int64_t lb, char *const Y[2], const int64_t LY[2], char *W, int64_t ldw,
+      int from, int to) {
+   const double hi = r->op->amg.lv[l].rho, lo = 0.25 * hi, tb = 0.5 * (hi + lo), dl = 0.5 * (hi - lo);
+   hipk_cheb_coef cf;
+   double rho = dl / tb;
+   int cur, first = 1;
+   memset(&cf, 0, sizeof(cf));
+   if (from < 0) {
+      cur = ((to - (steps - 1)) % 2 + 2) % 2;
+      for (int c = 0; c < r->nc; c++) cf.cx[c] = 1.0 / tb;
+      amg_update(r, l, &cf, 1, b, lb, NULL, 0, NULL, 0, NULL, 0, Y[cur], LY[cur]);
+      steps--;
+      first = 0;
+   } else cur = from;
+   for (int k = 0; k < steps; k++) {
+      double cy, cp, cx, cw;
+      amg_product(r, l, Y[cur], LY[cur], W, ldw);
+      if (first) { cy = 1.0; cp = 0.0; cx = 1.0 / tb; cw = -1.0 / tb; first = 0; }
+      else {
+         const double rn = 1.0 / (2.0 * tb / dl - rho), a = rn * rho, bb = 2.0 * rn / dl;
+         cy = 1.0 + a; cp = -a; cx = bb; cw = -bb;
+         rho = rn;
+      }
+      /* y_0 = 0 has no panel: the second iterate from zero has no y_{k-1} term */
+      const int has_prev = cp != 0.0 && !(from < 0 && k == 0);
+      for (int c = 0; c < r->nc; c++) { cf.cy[c] = cy; cf.cp[c] = cp; cf.cx[c] = cx; cf.cw[c] = cw; }
+      amg_update(r, l, &cf, 1, b, lb, W, ldw, Y[cur], LY[cur], has_prev ? Y[1 - cur] : NULL, LY[1 - cur], Y[1 - cur], LY[1 - cur]);
+      cur = 1 - cur;
+   }
+   return cur;
+}
+/* panel q of level l: level 0 has q = 0 (iterate) and 1 (product); the others 0 (right-hand side), 1, 2 (iterates), 3 (product) */
+static char *amg_panel(const amg_state *s, size_t es, int l, int q) {
+   size_t off = 0;
+   for (int k = 0; k < l; k++) off += (size_t)s->lv[k].ld * (k == 0 ? 2 : 4);
+   return (char *)s->buf + (off + (size_t)s->lv[l].ld * q) * s->cols * es;
+}
+/* the cycle at level l for the right-hand side b; the result goes to Y[0] */
+static void amg_vcycle(amg_run *r, int l, const char *b, int64_t lb, char *const Y[2], const int64_t LY[2], char *W, int64_t ldw) {
+   amg_state *s = &r->op->amg;
+   const amg_level_dev *L = &s->lv[l];
+   if (l == s->nlev - 1) {
+      if (s->G) {
+         if (!r->rc) { r->rc = hipk_amg_dense_apply(r->stream, r->dt, (int)L->n, s->G, r->nc, b, lb, Y[0], LY[0]); g_amg_launches++; }
+      } else (void)amg_cheb(r, l, s->cs, b, lb, Y, LY, W, ldw, -1, 0);
+      return;
+   }
+   const int a = s->nu % 2;                        /* the pre-smoothed iterate: nu post-smoothing steps later it is in Y[0] */
+   (void)amg_cheb(r, l, s->nu, b, lb, Y, LY, W, ldw, -1, a);
+   hipk_cheb_coef cf;                              /* the residual b - M y, over the product */
+   memset(&cf, 0, sizeof(cf));
+   for (int c = 0; c < r->nc; c++) { cf.cx[c] = 1.0; cf.cw[c] = -1.0; }
+   amg_product(r, l, Y[a], LY[a], W, ldw);
+   amg_update(r, l, &cf, 0, b, lb, W, ldw, NULL, 0, NULL, 0, W, ldw);
+   const int64_t ldc = s->lv[l + 1].ld, LYc[2] = {ldc, ldc};
+   char *bc = amg_panel(s, r->es, l + 1, 0), *Wc = amg_panel(s, r->es, l + 1, 3);
+   char *const Yc[2] = {amg_panel(s, r->es, l + 1, 1), amg_panel(s, r->es, l + 1, 2)};
+   if (!r->rc) { r->rc = hipk_amg_restrict(r->stream, r->dt, L->n, L->nc, L->aggptr, L->aggrows, r->nc, W, ldw, bc, ldc); g_amg_launches++; }
+   amg_vcycle(r, l + 1, bc, ldc, Yc, LYc, Wc, ldc);
+   if (!r->rc) { r->rc = hipk_amg_prolong_add(r->stream, r->dt, L->n, L->nc, L->agg, s->over, r->nc, Yc[0], ldc, Y[a], LY[a]); g_amg_launches++; }
+   (void)amg_cheb(r, l, s->nu, b, lb, Y, LY, W, ldw, a, 0);
+}
+
+extern "C" void primme_amd_amg_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
+      int *blockSize, struct primme_params *primme, int *ierr) {
+   primme_amd_operator *op = (primme_amd_operator *)primme->preconditioner;
+   void *stream = primme->queue ? (void *)*(hipStream_t *)primme->queue : NULL;
+   if (!op || op->amg.nlev < 1) { *ierr = 1; return; }
+   *ierr = 0;
+   if (*blockSize <= 0) return;
+   if (!stream) stream = hipk_ctx_stream(hipk_csr_ctx(op->A));
+   amg_state *s = &op->amg;
+   amg_run r;
+   r.op = op; r.stream = stream; r.dt = hipk_csr_dtype(op->A); r.es = op_elem(r.dt); r.rc = 0;
+   const int want = *blockSize < HIPK_CHEB_MAXCOLS ? *blockSize : HIPK_CHEB_MAXCOLS;
+   if (want > s->cols) {                           /* scratch for the widest chunk seen */
+      if (s->buf) (void)hipFree(s->buf);
+      s->buf = NULL; s->cols = 0;
+      size_t elems = 2 * (size_t)s->lv[0].ld;
+      for (int l = 1; l < s->nlev; l++) elems += 4 * (size_t)s->lv[l].ld;
+      if (hipMalloc(&s->buf, elems * r.es * want) != hipSuccess) { *ierr = 1; return; }
+      s->cols = want;
+   }
+   g_amg_levels = s->nlev;
+   for (int c0 = 0; c0 < *blockSize && !r.rc; c0 += HIPK_CHEB_MAXCOLS) {
+      r.nc = *blockSize - c0 < HIPK_CHEB_MAXCOLS ? *blockSize - c0 : HIPK_CHEB_MAXCOLS;
+      const char *xc = (const char *)x + (size_t)c0 * *ldx * r.es;
+      char *const Y[2] = {(char *)y + (size_t)c0 * *ldy * r.es, amg_panel(s, r.es, 0, 0)};
+      const int64_t LY[2] = {*ldy, s->lv[0].ld};
+      g_amg_applies += r.nc;
+      amg_vcycle(&r, 0, xc, *ldx, Y, LY, amg_panel(s, r.es, 0, 1), s->lv[0].ld);
    }
    if (r.rc) *ierr = 1;
 }

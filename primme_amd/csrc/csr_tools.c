@@ -8,6 +8,7 @@
  *   primme_amd_csr_complex_to_real  Hermitian matrix -> symmetric real-equivalent form
  *   primme_amd_csr_tile_plan      the row tiles, column windows and 16-bit index stream of the device CSR operator
  *   primme_amd_mg_plan            the grids and weights of the geometric multigrid preconditioner (primme_amd.h)
+ *   primme_amd_amg_plan_create    the aggregates and Galerkin matrices of the algebraic multigrid preconditioner
  *
  * Indices are 0-based int32 (the device kernels' format); values are double, complex as
  * (re, im) pairs.  Everything returned is malloc'ed; release with primme_amd_host_free. */
@@ -464,5 +465,237 @@ int primme_amd_mg_plan(const int dims[3], int *nlevels, int n[][3], double w[][3
       l++;
    }
    *nlevels = l + 1;
+   return 0;
+}
+
+/* ---- hierarchy of the aggregation algebraic multigrid preconditioner (primme_amd_io.h) ----------- */
+static void amg_level_free(primme_amd_amg_level *L) {
+   free(L->rowptr); free(L->colind); free(L->values); free(L->dinv); free(L->agg); free(L->aggptr); free(L->aggrows);
+   memset(L, 0, sizeof(*L));
+}
+void primme_amd_amg_plan_free(primme_amd_amg_plan *plan) {
+   if (!plan) return;
+   for (int l = 0; l < PRIMME_AMD_AMG_MAXLEVELS; l++) amg_level_free(&plan->level[l]);
+   free(plan);
+}
+static int amg_i32_cmp(const void *a, const void *b) {
+   const int32_t x = *(const int32_t *)a, y = *(const int32_t *)b;
+   return x < y ? -1 : x > y;
+}
+
+/* dg = diag(M_l); dinv and rho of the level.  -1: a row without a diagonal entry or with m_ii <= 0, -5: out of memory */
+static int amg_level_finish(primme_amd_amg_level *L, double *dg) {
+   L->dinv = (double *)malloc(sizeof(double) * (size_t)L->n);
+   if (!L->dinv) return -5;
+   double rho = 0.0;
+   for (int64_t i = 0; i < L->n; i++) {
+      double d = 0.0, s = 0.0;
+      int found = 0;
+      for (int32_t q = L->rowptr[i]; q < L->rowptr[i + 1]; q++) {
+         if (L->colind[q] == i) { d += L->values[q]; found = 1; }
+         s += fabs(L->values[q]);
+      }
+      if (!found || !(d > 0.0)) return -1;
+      dg[i] = d; L->dinv[i] = 1.0 / d;
+      if (s / d > rho) rho = s / d;
+   }
+   L->rho = rho;
+   return 0;
+}
+
+/* the three passes; agg[n] receives the aggregate of every row, returns the number of aggregates.  tmp: n int32 */
+static int64_t amg_aggregate(const primme_amd_amg_level *L, const double *dg, double theta, int32_t *agg, int32_t *tmp) {
+   const int64_t n = L->n;
+   const int32_t *rp = L->rowptr, *ci = L->colind;
+   const double *va = L->values;
+   int32_t nc = 0;
+#define AMG_STRONG(i, q) (ci[q] != (i) && fabs(va[q]) >= theta * sqrt(dg[i] * dg[ci[q]]))
+   for (int64_t i = 0; i < n; i++) agg[i] = tmp[i] = -1;
+   for (int64_t i = 0; i < n; i++) {                       /* pass 1 */
+      if (agg[i] >= 0) continue;
+      int ok = 1;
+      for (int32_t q = rp[i]; q < rp[i + 1] && ok; q++)
+         if (AMG_STRONG(i, q) && agg[ci[q]] >= 0) ok = 0;
+      if (!ok) continue;
+      agg[i] = nc;
+      for (int32_t q = rp[i]; q < rp[i + 1]; q++)
+         if (AMG_STRONG(i, q)) agg[ci[q]] = nc;
+      nc++;
+   }
+   for (int64_t i = 0; i < n; i++) {                       /* pass 2: agg holds the pass-1 aggregates until the loop is over */
+      if (agg[i] >= 0) continue;
+      int32_t best = -1;
+      double bv = -1.0;
+      for (int32_t q = rp[i]; q < rp[i + 1]; q++) {
+         if (!AMG_STRONG(i, q) || agg[ci[q]] < 0) continue;
+         const double v = fabs(va[q]);
+         const int32_t a = agg[ci[q]];
+         if (v > bv || (v == bv && a < best)) { bv = v; best = a; }
+      }
+      tmp[i] = best;
+   }
+   for (int64_t i = 0; i < n; i++)
+      if (agg[i] < 0) agg[i] = tmp[i];
+   for (int64_t i = 0; i < n; i++) {                       /* pass 3 */
+      if (agg[i] >= 0) continue;
+      agg[i] = nc;
+      for (int32_t q = rp[i]; q < rp[i + 1]; q++)
+         if (AMG_STRONG(i, q) && agg[ci[q]] < 0) agg[ci[q]] = nc;
+      nc++;
+   }
+#undef AMG_STRONG
+   return nc;
+}
+
+/* C = P' F P for the aggregates of F (F->nc, agg, aggptr, aggrows are set): row I adds the rows of aggregate I in ascending
+ * order, every row's entries in their order; columns sorted, one entry per position; then entry (J, I) takes the bits of
+ * (I, J), I < J, so that C is exactly symmetric when its pattern is */
+static int amg_galerkin(const primme_amd_amg_level *F, primme_amd_amg_level *Cl) {
+   const int64_t nc = F->nc;
+   Cl->n = nc;
+   Cl->rowptr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nc + 1));
+   Cl->colind = (int32_t *)malloc(sizeof(int32_t) * (size_t)(F->nnz > 0 ? F->nnz : 1));
+   Cl->values = (double *)malloc(sizeof(double) * (size_t)(F->nnz > 0 ? F->nnz : 1));
+   int32_t *mark = (int32_t *)malloc(sizeof(int32_t) * (size_t)nc), *list = (int32_t *)malloc(sizeof(int32_t) * (size_t)nc);
+   double *acc = (double *)malloc(sizeof(double) * (size_t)nc);
+   if (!Cl->rowptr || !Cl->colind || !Cl->values || !mark || !list || !acc) { free(mark); free(list); free(acc); return -5; }
+   for (int64_t J = 0; J < nc; J++) mark[J] = -1;
+   int32_t nnz = 0;
+   Cl->rowptr[0] = 0;
+   for (int64_t I = 0; I < nc; I++) {
+      int32_t cnt = 0;
+      for (int32_t p = F->aggptr[I]; p < F->aggptr[I + 1]; p++) {
+         const int32_t i = F->aggrows[p];
+         for (int32_t q = F->rowptr[i]; q < F->rowptr[i + 1]; q++) {
+            const int32_t J = F->agg[F->colind[q]];
+            if (mark[J] != (int32_t)I) { mark[J] = (int32_t)I; acc[J] = F->values[q]; list[cnt++] = J; }
+            else acc[J] += F->values[q];
+         }
+      }
+      qsort(list, (size_t)cnt, sizeof(int32_t), amg_i32_cmp);
+      for (int32_t k = 0; k < cnt; k++) { Cl->colind[nnz] = list[k]; Cl->values[nnz] = acc[list[k]]; nnz++; }
+      Cl->rowptr[I + 1] = nnz;
+   }
+   free(mark); free(list); free(acc);
+   Cl->nnz = nnz;
+   for (int64_t I = 0; I < nc; I++)
+      for (int32_t q = Cl->rowptr[I]; q < Cl->rowptr[I + 1]; q++) {
+         const int32_t J = Cl->colind[q];
+         if (J <= I) continue;
+         int32_t lo = Cl->rowptr[J], hi = Cl->rowptr[J + 1];
+         while (lo < hi) {
+            const int32_t mid = lo + (hi - lo) / 2;
+            if (Cl->colind[mid] < (int32_t)I) lo = mid + 1; else hi = mid;
+         }
+         if (lo < Cl->rowptr[J + 1] && Cl->colind[lo] == (int32_t)I) Cl->values[lo] = Cl->values[q];
+      }
+   return 0;
+}
+
+int primme_amd_amg_plan_create(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
+      double shift, double theta, primme_amd_amg_plan **plan) {
+   if (!plan) return -1;
+   *plan = NULL;
+   if (n < 1 || !rowptr || !colind || !values || (elem_size != 8 && elem_size != 4) || !(shift >= 0.0) || !(theta >= 0.0 && theta < 1.0)) return -1;
+   if (n > INT32_MAX) return -4;
+   primme_amd_amg_plan *P = (primme_amd_amg_plan *)calloc(1, sizeof(*P));
+   double *dg = (double *)malloc(sizeof(double) * (size_t)n);
+   int32_t *tmp = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
+   int rc = (P && dg && tmp) ? 0 : -5;
+   if (!rc) {
+      primme_amd_amg_level *L = &P->level[0];
+      const int64_t nnz = rowptr[n];
+      P->shift = shift; P->theta = theta;
+      L->n = n; L->nnz = nnz;
+      L->rowptr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+      L->colind = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1));
+      L->values = (double *)malloc(sizeof(double) * (size_t)(nnz > 0 ? nnz : 1));
+      if (!L->rowptr || !L->colind || !L->values) rc = -5;
+      else {
+         memcpy(L->rowptr, rowptr, sizeof(int32_t) * (size_t)(n + 1));
+         memcpy(L->colind, colind, sizeof(int32_t) * (size_t)nnz);
+         for (int64_t q = 0; q < nnz; q++) L->values[q] = elem_size == 8 ? ((const double *)values)[q] : (double)((const float *)values)[q];
+         for (int64_t i = 0; i < n && !rc; i++) {          /* + shift on the (first) diagonal entry of the row */
+            int32_t q = rowptr[i];
+            while (q < rowptr[i + 1] && (colind[q] < 0 || colind[q] >= n || colind[q] != i)) {
+               if (colind[q] < 0 || colind[q] >= n) rc = -1;
+               q++;
+            }
+            for (int32_t r = q; r < rowptr[i + 1]; r++)
+               if (colind[r] < 0 || colind[r] >= n) rc = -1;
+            if (q < rowptr[i + 1]) L->values[q] += shift; else rc = -1;
+         }
+      }
+      if (!rc) rc = amg_level_finish(L, dg);
+   }
+   int l = 0;
+   while (!rc) {
+      primme_amd_amg_level *L = &P->level[l];
+      if (L->n <= PRIMME_AMD_AMG_DENSE_ROWS || l + 1 >= PRIMME_AMD_AMG_MAXLEVELS) break;
+      int32_t *agg = (int32_t *)malloc(sizeof(int32_t) * (size_t)L->n);
+      if (!agg) { rc = -5; break; }
+      const int64_t nc = amg_aggregate(L, dg, theta, agg, tmp);
+      if ((double)nc > 0.8 * (double)L->n) { free(agg); break; }         /* stalled: this level is the last */
+      L->agg = agg; L->nc = nc;
+      L->aggptr = (int32_t *)calloc((size_t)(nc + 1), sizeof(int32_t));
+      L->aggrows = (int32_t *)malloc(sizeof(int32_t) * (size_t)L->n);
+      if (!L->aggptr || !L->aggrows) { rc = -5; break; }
+      for (int64_t i = 0; i < L->n; i++) L->aggptr[agg[i] + 1]++;
+      for (int64_t j = 0; j < nc; j++) L->aggptr[j + 1] += L->aggptr[j];
+      for (int64_t j = 0; j < nc; j++) tmp[j] = L->aggptr[j];
+      for (int64_t i = 0; i < L->n; i++) L->aggrows[tmp[agg[i]]++] = (int32_t)i;
+      rc = amg_galerkin(L, &P->level[l + 1]);
+      if (!rc) rc = amg_level_finish(&P->level[l + 1], dg);
+      l++;
+   }
+   free(dg); free(tmp);
+   if (rc) { primme_amd_amg_plan_free(P); return rc; }
+   P->nlevels = l + 1;
+   *plan = P;
+   return 0;
+}
+
+int primme_amd_amg_coarse_inverse(const primme_amd_amg_plan *plan, double *G) {
+   if (!plan || !G || plan->nlevels < 1) return -1;
+   const primme_amd_amg_level *L = &plan->level[plan->nlevels - 1];
+   const int n = (int)L->n;
+   if (L->n > PRIMME_AMD_AMG_DENSE_ROWS) return -1;
+   double *C = (double *)calloc((size_t)n * n, sizeof(double));
+   if (!C) return -5;
+   for (int i = 0; i < n; i++)
+      for (int32_t q = L->rowptr[i]; q < L->rowptr[i + 1]; q++) C[(size_t)i * n + L->colind[q]] += L->values[q];
+   /* M = C C' (lower triangle of C, row-major) */
+   for (int j = 0; j < n; j++) {
+      double d = C[(size_t)j * n + j];
+      for (int k = 0; k < j; k++) d -= C[(size_t)j * n + k] * C[(size_t)j * n + k];
+      if (!(d > 0.0)) { free(C); return -1; }
+      d = sqrt(d);
+      C[(size_t)j * n + j] = d;
+      for (int i = j + 1; i < n; i++) {
+         double s = C[(size_t)i * n + j];
+         for (int k = 0; k < j; k++) s -= C[(size_t)i * n + k] * C[(size_t)j * n + k];
+         C[(size_t)i * n + j] = s / d;
+      }
+   }
+   /* column c of the inverse: C z = e_c, C' g = z */
+   for (int c = 0; c < n; c++) {
+      double *g = G + (size_t)c * n;
+      for (int i = 0; i < n; i++) {
+         double s = i == c ? 1.0 : 0.0;
+         for (int k = c; k < i; k++) s -= C[(size_t)i * n + k] * g[k];
+         g[i] = i < c ? 0.0 : s / C[(size_t)i * n + i];
+      }
+      for (int i = n - 1; i >= 0; i--) {
+         double s = g[i];
+         for (int k = i + 1; k < n; k++) s -= C[(size_t)k * n + i] * g[k];
+         g[i] = s / C[(size_t)i * n + i];
+      }
+   }
+   free(C);
+   for (int i = 0; i < n; i++)
+      for (int j = 0; j < i; j++) {
+         const double s = 0.5 * (G[(size_t)i * n + j] + G[(size_t)j * n + i]);
+         G[(size_t)i * n + j] = G[(size_t)j * n + i] = s;
+      }
    return 0;
 }
