@@ -400,6 +400,8 @@ int hipk_copy_cols(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const void *X, int64
    return 0;
 }
 int hipk_pair_rotate(hipk_ctx *ctx, hipk_dtype dt, int64_t npairs, const void *X, int64_t ldX, void *Y, int64_t ldY, int nx) {
+   if (nx <= 0 || npairs <= 0) return 0;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;      /* dt is the real type of the parts */
    (void)ctx;
    for (int c = 0; c < nx; c++) {
       if (dt == HIPK_F64) {
@@ -463,12 +465,18 @@ int hipk_xpay_cols(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const double *a, con
 }
 int hipk_axpy_dot(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, const double *a, const void *X, int64_t ldX,
       void *Y, int64_t ldY, const void *Z, int64_t ldZ, double *out) {
+   if (nx <= 0) return 0;
+   if (nx > 64) return -1;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    int rc = hipk_axpy_cols(ctx, dt, m, a, X, ldX, Y, ldY, nx);
    if (rc) return rc;
    return hipk_pair_dots(ctx, dt, m, Z ? Z : Y, Z ? ldZ : ldY, Y, ldY, nx, out);
 }
 int hipk_qmr_update(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, const double *gam, const double *eta,
       const void *D, int64_t ldD, void *Delta, int64_t ldDelta, void *Sol, int64_t ldSol, double *dotsol) {
+   if (nx <= 0) return 0;
+   if (nx > 64) return -1;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    (void)ctx;
    for (int c = 0; c < nx; c++) {
       const void *d = colp(dt, D, ldD, c); void *de = (void *)colp(dt, Delta, ldDelta, c); void *so = (void *)colp(dt, Sol, ldSol, c);
@@ -615,6 +623,8 @@ int hipk_csr_matvec_scaled(hipk_csr *A, hipk_ctx *ctx, const void *x, const doub
 
 int hipk_triple_dots(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const void *X, int64_t ldX, const void *V, int64_t ldV,
       const void *W, int64_t ldW, int nx, double *out) {
+   if (nx <= 0) return 0;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    (void)ctx;
    for (int c = 0; c < nx; c++) {
       const void *x = colp(dt, X, ldX, c), *v = colp(dt, V, ldV, c), *w = colp(dt, W, ldW, c);
@@ -642,6 +652,9 @@ int hipk_project_triple_dots(hipk_ctx *ctx, hipk_dtype dt, int64_t m, const hipk
 }
 int hipk_axpy_proj_dot(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, const double *alpha, const double *xr, const void *W,
       int64_t ldW, const void *X, int64_t ldX, void *G, int64_t ldG, double *out) {
+   if (nx <= 0) return 0;
+   if (nx > 64) return -1;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    (void)ctx;
    for (int c = 0; c < nx; c++) {
       const void *w = colp(dt, W, ldW, c), *x = colp(dt, X, ldX, c);
@@ -688,6 +701,7 @@ int hipk_axpy_proj_dot_jacobi_dev(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int n
       double min_den, double *out_dev) {
    if (nx <= 0) return 0;
    if (nx > 8 || !tri_dev) return -1;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    double al[8], xr[8];
    for (int c = 0; c < nx; c++) qmr_alpha_cpu(tri_dev, nx, c, rho_prev_host[c], mach_eps, &al[c], &xr[c]);
    return hipk_axpy_proj_dot_jacobi(ctx, dt, m, nx, al, xr, W, ldW, X, ldX, G, ldG, diag, shift_host, min_den, out_dev);
@@ -698,6 +712,7 @@ int hipk_qmr_update_dir_dev(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, con
       double min_den, double *dotsol_dev) {
    if (nx <= 0) return 0;
    if (nx > 8 || !tri_dev || !ggr_dev) return -1;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    double out[8];
    for (int c = 0; c < nx; c++) {
       double a, xr;
@@ -728,6 +743,9 @@ int hipk_qmr_update_dir_dev(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, con
 int hipk_qmr_update_jacobi(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, const double *gam, const double *eta,
       const void *D, int64_t ldD, void *Delta, int64_t ldDelta, void *Sol, int64_t ldSol, const void *G, int64_t ldG,
       const void *diag, const double *shift, double min_den, void *W, int64_t ldW, double *out) {
+   if (nx <= 0) return 0;
+   if (nx > 64) return -1;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    (void)ctx;
    if (!(min_den > 0.0)) min_den = 1e-300;
    for (int c = 0; c < nx; c++) {
@@ -739,7 +757,7 @@ int hipk_qmr_update_jacobi(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, cons
          st_(dt, so, i, ld_(dt, de, i) + ld_(dt, so, i));
          s1 += ld_(dt, so, i) * ld_(dt, so, i);
          double den = ld_(dt, diag, i) - (shift ? shift[c] : 0.0);
-         if (!(fabs(den) > min_den)) den = copysign(min_den, den);
+         if (fabs(den) <= min_den) den = copysign(min_den, den);       /* a NaN stays a NaN */
          st_(dt, w, i, ld_(dt, g, i) / den);
          s2 += ld_(dt, g, i) * ld_(dt, w, i);
       }
@@ -751,6 +769,9 @@ int hipk_qmr_update_jacobi(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, cons
 
 int hipk_axpy_proj_dot_jacobi(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, const double *alpha, const double *xr, const void *W,
       int64_t ldW, const void *X, int64_t ldX, void *G, int64_t ldG, const void *diag, const double *shift, double min_den, double *out) {
+   if (nx <= 0) return 0;
+   if (nx > 64) return -1;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    (void)ctx;
    if (!(min_den > 0.0)) min_den = 1e-300;
    for (int c = 0; c < nx; c++) {
@@ -764,7 +785,7 @@ int hipk_axpy_proj_dot_jacobi(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, c
          const double gi = ld_(dt, g, i);
          s1 += gi * gi;
          double den = ld_(dt, diag, i) - (shift ? shift[c] : 0.0);
-         if (!(fabs(den) > min_den)) den = copysign(min_den, den);
+         if (fabs(den) <= min_den) den = copysign(min_den, den);       /* a NaN stays a NaN */
          double wi = gi / den;
          if (dt == HIPK_F32) wi = (double)(float)wi;
          s2 += gi * wi;
@@ -777,6 +798,9 @@ int hipk_axpy_proj_dot_jacobi(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, c
 int hipk_qmr_update_dir(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, const double *gam, const double *eta, const double *beta,
       void *D, int64_t ldD, void *Delta, int64_t ldDelta, void *Sol, int64_t ldSol, const void *G, int64_t ldG,
       const void *diag, const double *shift, double min_den, double *out) {
+   if (nx <= 0) return 0;
+   if (nx > 64) return -1;
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
    (void)ctx;
    if (!(min_den > 0.0)) min_den = 1e-300;
    for (int c = 0; c < nx; c++) {
@@ -789,7 +813,7 @@ int hipk_qmr_update_dir(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, const d
          st_(dt, so, i, ld_(dt, de, i) + ld_(dt, so, i));
          s1 += ld_(dt, so, i) * ld_(dt, so, i);
          double den = ld_(dt, diag, i) - (shift ? shift[c] : 0.0);
-         if (!(fabs(den) > min_den)) den = copysign(min_den, den);
+         if (fabs(den) <= min_den) den = copysign(min_den, den);       /* a NaN stays a NaN */
          double wi = ld_(dt, g, i) / den;
          if (dt == HIPK_F32) wi = (double)(float)wi;
          st_(dt, d, i, wi + beta[c] * di);
@@ -802,6 +826,8 @@ int hipk_qmr_update_dir(hipk_ctx *ctx, hipk_dtype dt, int64_t m, int nx, const d
 
 int hipk_jacobi_apply(void *stream, hipk_dtype dt, int64_t m, const void *diag, const double *shift,
       double min_den, const void *x, int64_t ldx, void *y, int64_t ldy, int ncols) {
+   if (ncols <= 0) return 0;
+   if (ncols > 64) return -1;
    (void)stream;
    if (!(min_den > 0.0)) min_den = 1e-300;
    if (IS_Z(dt)) return hipk_z_jacobi_apply(dt, m, diag, shift, min_den, x, ldx, y, ldy, ncols);
@@ -809,7 +835,7 @@ int hipk_jacobi_apply(void *stream, hipk_dtype dt, int64_t m, const void *diag, 
       const void *xc = colp(dt, x, ldx, c); void *yc = (void *)colp(dt, y, ldy, c);
       for (int64_t i = 0; i < m; i++) {
          double d = ld_(dt, diag, i) - (shift ? shift[c] : 0.0);
-         if (!(fabs(d) > min_den)) d = copysign(min_den, d);
+         if (fabs(d) <= min_den) d = copysign(min_den, d);           /* a NaN stays a NaN */
          st_(dt, yc, i, ld_(dt, xc, i) / d);
       }
    }

@@ -197,7 +197,7 @@ int hipk_z_jacobi_apply(hipk_dtype dt, int64_t m, const void *diag, const double
       const void *xc = zcol(dt, x, ldx, c); void *yc = (void *)zcol(dt, y, ldy, c);
       for (int64_t i = 0; i < m; i++) {
          double d = creal(ldz(dt, diag, i)) - (shift ? shift[c] : 0.0);
-         if (!(fabs(d) > min_den)) d = copysign(min_den, d);
+         if (fabs(d) <= min_den) d = copysign(min_den, d);           /* a NaN stays a NaN */
          stz(dt, yc, i, ldz(dt, xc, i) / d);
       }
    }

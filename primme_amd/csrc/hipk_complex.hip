@@ -806,7 +806,7 @@ zjacobi_kernel(const cpx<R> *__restrict__ diag, ZShift sh, double min_den, const
    for (int c = 0; c < ncols; c++)
       for (int64_t i = (int64_t)blockIdx.x * HIPK_BLOCK + threadIdx.x; i < m; i += stride) {
          double d = (double)diag[i].re - sh.s[c];
-         if (!(fabs(d) > min_den)) d = copysign(min_den, d);
+         if (fabs(d) <= min_den) d = copysign(min_den, d);           /* a NaN stays a NaN */
          const zacc xv = zload(x + (size_t)c * ldx + i);
          zstore(y + (size_t)c * ldy + i, zacc{xv.re / d, xv.im / d});
       }

@@ -247,7 +247,7 @@ qmr_update_jacobi_kernel(ColScal gam, ColScal eta, ColScal shf, double min_den, 
             Sol[i + cc * ldSol] = ns;
             s1[c] = fma((double)ns, (double)ns, s1[c]);
             double den = dg - shf.a[c0 + c];
-            if (!(fabs(den) > min_den)) den = copysign(min_den, den);
+            if (fabs(den) <= min_den) den = copysign(min_den, den);       /* a NaN stays a NaN */
             const double gi = (double)G[i + cc * ldG];
             const T wi = (T)(gi / den);
             Wp[i + cc * ldW] = wi;
@@ -389,7 +389,7 @@ axpy_proj_dot_jacobi_kernel(ColScal alpha, ColScal xr, ColScal shf, double min_d
             G[i + cc * ldG] = ng;
             s1[c] = fma((double)ng, (double)ng, s1[c]);
             double den = dg - shf.a[c0 + c];
-            if (!(fabs(den) > min_den)) den = copysign(min_den, den);
+            if (fabs(den) <= min_den) den = copysign(min_den, den);       /* a NaN stays a NaN */
             const T wi = (T)((double)ng / den);                      /* rounded like the stored K^-1 g */
             s2[c] = fma((double)ng, (double)wi, s2[c]);
          }
@@ -449,7 +449,7 @@ qmr_update_dir_kernel(ColScal gam, ColScal eta, ColScal bet, ColScal shf, double
             Sol[i + cc * ldSol] = ns;
             s1[c] = fma((double)ns, (double)ns, s1[c]);
             double den = dg - shf.a[c0 + c];
-            if (!(fabs(den) > min_den)) den = copysign(min_den, den);
+            if (fabs(den) <= min_den) den = copysign(min_den, den);       /* a NaN stays a NaN */
             const T wi = (T)((double)G[i + cc * ldG] / den);
             D[i + cc * ldD] = (T)fma(be[c], di, (double)wi);    /* w += beta d, as the axpy pass rounds it */
          }
@@ -820,7 +820,7 @@ jacobi_kernel(const T *__restrict__ diag, JacShift sh, double min_den, const T *
       for (int64_t i = (int64_t)blockIdx.x * HIPK_BLOCK + threadIdx.x; i < m; i += stride) {
          double d = (double)diag[i] - shift;
          /* same guard as the reference's test preconditioner: avoid dividing by ~0 */
-         if (!(fabs(d) > min_den)) d = copysign(min_den, d);
+         if (fabs(d) <= min_den) d = copysign(min_den, d);           /* a NaN stays a NaN */
          y[i + (size_t)c * ldy] = (T)((double)x[i + (size_t)c * ldx] / d);
       }
    }
