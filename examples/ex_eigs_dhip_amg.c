@@ -2,13 +2,16 @@
  * tests/golden/reference_driver/LUNDA.mtx), 4 smallest eigenvalues, eps 1e-10, solved with GD+k twice through the C ABI of
  * libprimme_amd.so: with the Jacobi preconditioner and with the aggregation algebraic multigrid preconditioner
  * primme_amd_amg_precond (one V(2,2) cycle per vector on a hierarchy that the library aggregates from the CSR arrays; theta
- * 0.08, over 1, shift 0).  Prints both outer-iteration counts.
+ * 0.08, over 1, shift 0).  Prints both outer-iteration counts.  With --smoothed after the matrix the second solve uses the
+ * hierarchy of smoothed aggregation instead (primme_amd_operator_set_amg_smoothed, omega 4/3).
  *
- *   make -C examples && examples/ex_eigs_dhip_amg matrix.mtx     (exit code 0 = both solves converged to the same eigenvalues)
+ *   make -C examples && examples/ex_eigs_dhip_amg matrix.mtx [--smoothed]     (exit code 0 = both solves converged to the same
+ *   eigenvalues)
  */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include "primme_amd.h"
 #include "primme_amd_kernels.h"
 #include "primme_amd_comm.h"
@@ -30,7 +33,8 @@ static int solve(primme_amd_operator *op, hipk_ctx *ctx, int n, double aNorm, co
    primme.preconditioner = op;
    primme.correctionParams.precondition = 1;
    if (amg) {
-      if (primme_amd_operator_set_amg(op, rp, ci, va, 2, 16, 0.08, 1.0, 0.0)) return 1;
+      if (amg == 2 ? primme_amd_operator_set_amg_smoothed(op, rp, ci, va, 2, 16, 0.08, 4.0 / 3.0, 0.0)
+                   : primme_amd_operator_set_amg(op, rp, ci, va, 2, 16, 0.08, 1.0, 0.0)) return 1;
       primme.applyPreconditioner = primme_amd_amg_precond;
    } else {
       primme_amd_operator_set_jacobi(op, 0, 0.0);              /* K = diag(A) - the solver's shift of each vector */
@@ -45,7 +49,7 @@ static int solve(primme_amd_operator *op, hipk_ctx *ctx, int n, double aNorm, co
    long applies = 0, launches = 0, levels = 0;
    primme_amd_amg_stats(&applies, &launches, &levels);
    int bad = (ret != 0 || primme.initSize != NEV);
-   printf("%s: hip_dprimme returned %d, %d pairs, %lld outer iterations, %lld matvecs", amg ? "amg" : "jacobi", ret, primme.initSize,
+   printf("%s: hip_dprimme returned %d, %d pairs, %lld outer iterations, %lld matvecs", amg == 2 ? "amg (smoothed)" : amg ? "amg" : "jacobi", ret, primme.initSize,
          (long long)primme.stats.numOuterIterations, (long long)primme.stats.numMatvecs);
    if (amg) printf(", %ld vectors preconditioned in %ld launches on %ld levels", applies, launches, levels);
    printf("\n");
@@ -60,7 +64,8 @@ static int solve(primme_amd_operator *op, hipk_ctx *ctx, int n, double aNorm, co
 }
 
 int main(int argc, char **argv) {
-   if (argc < 2) { fprintf(stderr, "usage: %s matrix.mtx\n", argv[0]); return 2; }
+   if (argc < 2 || (argc > 2 && strcmp(argv[2], "--smoothed"))) { fprintf(stderr, "usage: %s matrix.mtx [--smoothed]\n", argv[0]); return 2; }
+   const int smoothed = argc > 2;
    int64_t m, n, nnz;
    int32_t *rp, *ci;
    double *va;
@@ -86,7 +91,7 @@ int main(int argc, char **argv) {
    long long jac = 0, amg = 0;
    double ej[NEV], ea[NEV];
    int bad = solve(op, ctx, (int)n, aNorm, rp, ci, va, 0, ej, &jac);
-   bad |= solve(op, ctx, (int)n, aNorm, rp, ci, va, 1, ea, &amg);
+   bad |= solve(op, ctx, (int)n, aNorm, rp, ci, va, smoothed ? 2 : 1, ea, &amg);
    printf("outer iterations with the Jacobi preconditioner: %lld\nouter iterations with the algebraic multigrid preconditioner: %lld\n", jac, amg);
    for (int k = 0; k < NEV; k++)
       if (!(fabs(ej[k] - ea[k]) <= 2e-10 * aNorm)) bad = 1;      /* each within its residual bound eps |A| of an eigenvalue */

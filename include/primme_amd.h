@@ -366,7 +366,21 @@ void primme_amd_multigrid_stats(long *applies, long *launches);
  * allocated at the first application and freed with the operator; block columns beyond 8 are processed in chunks.  The
  * products inside are not counted in numMatvecs.
  * primme_amd_amg_stats: for this process since the last call, the vectors preconditioned, the launches (kernels and level
- * products) and the levels of the hierarchy applied last. */
+ * products) and the levels of the hierarchy applied last.
+ *
+ * Smoothed aggregation:
+ *    primme_amd_operator_set_amg_smoothed(op, rowptr_host, colind_host, values_host, smooth_steps, coarse_steps, theta, omega,
+ *    shift)   (usual values 2, 16, 0.08, 4/3, 0.0), then the same two members of primme_params.
+ * The hierarchy is that of primme_amd_amg_plan_create_smoothed: P_l = (I - (omega / rho_l) D_l^-1 M_l) T_l for the 0/1 matrix
+ * T_l of the same aggregates and M_{l+1} = P_l' M_l P_l.  The cycle is the one above with the restriction and interpolation
+ * through hipk_amg_csr_apply on P_l' and P_l, both uploaded in CSR with double values, and over = 1; K is symmetric positive
+ * definite as before, since P_l' is the exact transpose and the post-smoother is the same construction.  11 launches per level
+ * and chunk, like the plain cycle.  Extra device memory: about 2 nnz(P_l) 12 bytes per level (P_l and P_l', an int32 index
+ * and a double per entry; nnz(P_0) is about 2.5 n for the 5-point Laplacian), besides the coarse matrices, which are denser
+ * than those of plain aggregation.  Preconditions and return codes as set_amg; -1 also for omega outside (0, 2).
+ * primme_amd_amg_precond and primme_amd_amg_stats serve both. */
+int primme_amd_operator_set_amg_smoothed(struct primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smooth_steps, int coarse_steps, double theta, double omega, double shift);
 int primme_amd_operator_set_amg(struct primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
       const void *values_host, int smooth_steps, int coarse_steps, double theta, double over, double shift);
 void primme_amd_amg_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,

@@ -122,7 +122,16 @@ void primme_amd_tile_plan_free(primme_amd_tile_plan *P);
  * primme_amd_amg_plan_create returns 0 and *plan (release with primme_amd_amg_plan_free), -1 for n < 1, theta outside [0, 1),
  * shift < 0, a row without a diagonal entry or a diagonal entry <= 0 on any level, -4 beyond int32, -5 out of memory.
  * primme_amd_amg_coarse_inverse writes G = M_L^-1 (n_L x n_L, symmetric, n_L <= PRIMME_AMD_AMG_DENSE_ROWS) of the last
- * level from a Cholesky factorisation; -1 when M_L is not positive definite or has more rows. */
+ * level from a Cholesky factorisation; -1 when M_L is not positive definite or has more rows.
+ *
+ * primme_amd_amg_plan_create_smoothed builds the hierarchy of SMOOTHED aggregation with the same
+ * aggregation passes, stop rules, per-level data and error returns.  T_l being the 0/1 matrix of agg_l,
+ *    P_l = (I - (omega / rho_l) D_l^-1 M_l) T_l         (M_l unfiltered, the columns of T_l not normalised)
+ *    M_{l+1} = P_l' M_l P_l                             (a general sparse triple product in double)
+ * with sorted columns and one entry per position in both; the upper triangle of M_{l+1} is computed and mirrored, so it is
+ * exactly symmetric.  transfer[l] of every level but the last holds P_l in CSR (n_l rows, pnnz entries) and its explicit
+ * transpose R_l = P_l' in CSR (nc_l rows, ascending columns, the values the same bits); the plain plan leaves transfer[] NULL
+ * and omega 0.  omega in (0, 2), 4/3 the usual choice; outside: -1.  -4 also when nnz(P_l) or nnz(M_{l+1}) passes int32. */
 #define PRIMME_AMD_AMG_MAXLEVELS 24
 #define PRIMME_AMD_AMG_DENSE_ROWS 256
 typedef struct primme_amd_amg_level {
@@ -132,13 +141,24 @@ typedef struct primme_amd_amg_level {
    double rho;
    int32_t *agg, *aggptr, *aggrows;
 } primme_amd_amg_level;
+typedef struct primme_amd_amg_transfer {
+   int64_t pnnz;
+   int32_t *prowptr, *pcolind;   /* P_l: n + 1, pnnz */
+   double *pvalues;
+   int32_t *rrowptr, *rcolind;   /* R_l = P_l': nc + 1, pnnz */
+   double *rvalues;
+} primme_amd_amg_transfer;
 typedef struct primme_amd_amg_plan {
    int nlevels;
    double shift, theta;
    primme_amd_amg_level level[PRIMME_AMD_AMG_MAXLEVELS];
+   double omega;                 /* 0: plain aggregation */
+   primme_amd_amg_transfer transfer[PRIMME_AMD_AMG_MAXLEVELS];
 } primme_amd_amg_plan;
 int primme_amd_amg_plan_create(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
       double shift, double theta, primme_amd_amg_plan **plan);
+int primme_amd_amg_plan_create_smoothed(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
+      double shift, double theta, double omega, primme_amd_amg_plan **plan);
 void primme_amd_amg_plan_free(primme_amd_amg_plan *plan);
 int primme_amd_amg_coarse_inverse(const primme_amd_amg_plan *plan, double *G);
 void primme_amd_host_free(void *p);

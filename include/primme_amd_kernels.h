@@ -487,9 +487,17 @@ int hipk_mg_prolong_add(void *hip_stream, hipk_dtype dt, const int nf[3], const 
  *   hipk_amg_prolong_add    Y[i] += over C[agg[i]], nf rows
  *   hipk_amg_dense_apply    Y = G X, G dense symmetric n x n in double, n <= PRIMME_AMD_AMG_DENSE_ROWS (primme_amd_io.h);
  *                           one launch, element accesses (a column is at most 2 KB); Y may be X
- * aggptr (nc + 1), aggrows (nf) and agg (nf) are DEVICE arrays of the library's own making (from primme_amd_amg_plan_create):
- * the entry points check sizes and pointers and TRUST the indices — an index out of range is an access out of range.
- * -1: argument error (rows < 1, nc > nf, more than HIPK_CHEB_MAXCOLS columns, a NULL panel that is needed, F == C, C == Y). */
+ *   hipk_amg_csr_apply      Out = T In (accumulate = 0) or Out += T In (accumulate = 1), T an nrows x ncols CSR matrix with
+ *                           DOUBLE values: the restriction (T = P_l', accumulate 0) and the interpolation (T = P_l,
+ *                           accumulate 1) of smoothed aggregation.  A lane owns 16 bytes of consecutive rows of Out (one
+ *                           element where Out is not aligned); a row of at most 64 entries is summed by its lane in
+ *                           ascending position, a longer one by the wave as in hipk_amg_restrict; In is read by element
+ *                           through colind.  No LDS
+ * aggptr (nc + 1), aggrows (nf), agg (nf), rowptr (nrows + 1), colind and values are DEVICE arrays of the library's own making
+ * (from primme_amd_amg_plan_create and _create_smoothed): the entry points check sizes and pointers and TRUST the indices — an
+ * index out of range is an access out of range.
+ * -1: argument error (rows < 1, nc > nf, ncols < 1, more than HIPK_CHEB_MAXCOLS columns, a NULL panel or array that is needed,
+ * F == C, C == Y, In == Out). */
 int hipk_amg_smooth_update(void *hip_stream, hipk_dtype dt, int64_t m, int nx, const hipk_cheb_coef *coef, const double *dinv,
       const void *X, int64_t ldx, const void *W, int64_t ldw, const void *Yk, int64_t ldk, const void *Yprev, int64_t ldp,
       void *Out, int64_t ldo);
@@ -497,6 +505,8 @@ int hipk_amg_restrict(void *hip_stream, hipk_dtype dt, int64_t nf, int64_t nc, c
       const void *F, int64_t ldf, void *C, int64_t ldc);
 int hipk_amg_prolong_add(void *hip_stream, hipk_dtype dt, int64_t nf, int64_t nc, const int32_t *agg, double over, int nx,
       const void *C, int64_t ldc, void *Y, int64_t ldy);
+int hipk_amg_csr_apply(void *hip_stream, hipk_dtype dt, int64_t nrows, int64_t ncols, const int32_t *rowptr, const int32_t *colind,
+      const double *values, int accumulate, int nx, const void *In, int64_t ldin, void *Out, int64_t ldout);
 int hipk_amg_dense_apply(void *hip_stream, hipk_dtype dt, int n, const double *G, int nx, const void *X, int64_t ldx, void *Y,
       int64_t ldy);
 

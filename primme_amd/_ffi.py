@@ -355,6 +355,10 @@ def declare_amg(lib):
     lib.hipk_amg_restrict.restype = C.c_int
     lib.hipk_amg_prolong_add.argtypes = [_vp, _i, _i64, _i64, _vp, C.c_double, _i, _vp, _i64, _vp, _i64]
     lib.hipk_amg_prolong_add.restype = C.c_int
+    lib.primme_amd_operator_set_amg_smoothed.argtypes = [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double]
+    lib.primme_amd_operator_set_amg_smoothed.restype = C.c_int
+    lib.hipk_amg_csr_apply.argtypes = [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _i64]
+    lib.hipk_amg_csr_apply.restype = C.c_int
     lib.hipk_amg_dense_apply.argtypes = [_vp, _i, _i, _vp, _i, _vp, _i64, _vp, _i64]
     lib.hipk_amg_dense_apply.restype = C.c_int
 

@@ -15,13 +15,16 @@
    shift folded into the product), dinv = 1 / diag(M_l), the spectral bound rho and the aggregate maps; ld elements per scratch
    column (16-byte columns).  G: the dense inverse of the last level when it has at most PRIMME_AMD_AMG_DENSE_ROWS rows.
    buf: ONE allocation of cols columns per panel, level 0 an iterate and the product, every other level the right-hand side,
-   two iterates and the product */
+   two iterates and the product.  Smoothed aggregation (set_amg_smoothed): P_l (n rows) and R_l = P_l' (nc rows) in CSR with
+   double values, NULL for plain aggregation */
 struct amg_level_dev {
    int64_t n, nc, ld;
    double rho;
    hipk_csr *M;
    double *dinv;
    int32_t *agg, *aggptr, *aggrows;
+   int32_t *prp, *pci, *rrp, *rci;
+   double *pva, *rva;
 };
 struct amg_state {
    int nlev, nu, cs, cols;
@@ -584,7 +587,9 @@ extern "C" void primme_amd_multigrid_precond(void *x, PRIMME_INT *ldx, void *y, 
  * polynomial p and makes K symmetric (the construction of 4n).  A step is the level product (hipk_csr_matvec; level 0 the
  * operator's own matrix, hipk_csr_matvec_shifted adding the shift) and one hipk_amg_smooth_update.  The iterates of a level
  * alternate between two panels, y_{k+1} over y_{k-1}; a sequence starts in the panel that makes its last iterate land where
- * the next stage expects it (the result of a level in panel 0; level 0: the caller's y). */
+ * the next stage expects it (the result of a level in panel 0; level 0: the caller's y).
+ * With the hierarchy of primme_amd_amg_plan_create_smoothed the restriction and the interpolation of a level
+ * are hipk_amg_csr_apply on R_l = P_l' and P_l, over = 1; everything else is the same. */
 static long g_amg_applies, g_amg_launches, g_amg_levels;
 extern "C" void primme_amd_amg_stats(long *applies, long *launches, long *levels) {
    if (applies) *applies = g_amg_applies;
@@ -601,6 +606,12 @@ static void amg_release(amg_state *s) {
       if (L->agg) (void)hipFree(L->agg);
       if (L->aggptr) (void)hipFree(L->aggptr);
       if (L->aggrows) (void)hipFree(L->aggrows);
+      if (L->prp) (void)hipFree(L->prp);
+      if (L->pci) (void)hipFree(L->pci);
+      if (L->pva) (void)hipFree(L->pva);
+      if (L->rrp) (void)hipFree(L->rrp);
+      if (L->rci) (void)hipFree(L->rci);
+      if (L->rva) (void)hipFree(L->rva);
    }
    if (s->G) (void)hipFree(s->G);
    if (s->buf) (void)hipFree(s->buf);
@@ -612,8 +623,9 @@ static int amg_to_device(hipk_ctx *ctx, void **dst, const void *src, size_t byte
    return bytes ? hipk_upload(ctx, *dst, src, bytes) : 0;
 }
 
-extern "C" int primme_amd_operator_set_amg(primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
-      const void *values_host, int smooth_steps, int coarse_steps, double theta, double over, double shift) {
+/* omega = 0: plain aggregation with the over-correction `over`; omega in (0, 2): smoothed aggregation, over = 1 */
+static int amg_configure(primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smooth_steps, int coarse_steps, double theta, double over, double omega, double shift) {
    if (!op) return -1;
    const hipk_dtype dt = hipk_csr_dtype(op->A);
    if (op->mode != 0 || (op->comm && primme_amd_comm_size(op->comm) > 1) || op->ldscale != 1 || (dt != HIPK_F64 && dt != HIPK_F32)) return -44;
@@ -623,7 +635,9 @@ extern "C" int primme_amd_operator_set_amg(primme_amd_operator *op, const int32_
    const int64_t n = hipk_csr_nrows(op->A);
    if (n < 1 || rowptr_host[0] != 0 || (int64_t)rowptr_host[n] != hipk_csr_nnz(op->A)) return -1;
    primme_amd_amg_plan *P = NULL;
-   if (primme_amd_amg_plan_create(n, rowptr_host, colind_host, values_host, dt == HIPK_F64 ? 8 : 4, shift, theta, &P)) return -1;
+   if (omega == 0.0 ? primme_amd_amg_plan_create(n, rowptr_host, colind_host, values_host, dt == HIPK_F64 ? 8 : 4, shift, theta, &P)
+                    : primme_amd_amg_plan_create_smoothed(n, rowptr_host, colind_host, values_host, dt == HIPK_F64 ? 8 : 4, shift, theta, omega, &P))
+      return -1;
    hipk_ctx *ctx = hipk_csr_ctx(op->A);
    amg_state s;
    memset(&s, 0, sizeof(s));
@@ -649,6 +663,15 @@ extern "C" int primme_amd_operator_set_amg(primme_amd_operator *op, const int32_
          if (!rc) rc = amg_to_device(ctx, (void **)&L->aggptr, H->aggptr, sizeof(int32_t) * (size_t)(H->nc + 1));
          if (!rc) rc = amg_to_device(ctx, (void **)&L->aggrows, H->aggrows, sizeof(int32_t) * (size_t)H->n);
       }
+      const primme_amd_amg_transfer *X = &P->transfer[l];
+      if (!rc && H->nc > 0 && X->prowptr) {
+         rc = amg_to_device(ctx, (void **)&L->prp, X->prowptr, sizeof(int32_t) * (size_t)(H->n + 1));
+         if (!rc) rc = amg_to_device(ctx, (void **)&L->pci, X->pcolind, sizeof(int32_t) * (size_t)X->pnnz);
+         if (!rc) rc = amg_to_device(ctx, (void **)&L->pva, X->pvalues, sizeof(double) * (size_t)X->pnnz);
+         if (!rc) rc = amg_to_device(ctx, (void **)&L->rrp, X->rrowptr, sizeof(int32_t) * (size_t)(H->nc + 1));
+         if (!rc) rc = amg_to_device(ctx, (void **)&L->rci, X->rcolind, sizeof(int32_t) * (size_t)X->pnnz);
+         if (!rc) rc = amg_to_device(ctx, (void **)&L->rva, X->rvalues, sizeof(double) * (size_t)X->pnnz);
+      }
    }
    const int64_t nl = P->level[P->nlevels - 1].n;
    if (!rc && nl <= PRIMME_AMD_AMG_DENSE_ROWS) {
@@ -662,6 +685,17 @@ extern "C" int primme_amd_operator_set_amg(primme_amd_operator *op, const int32_
    amg_release(&op->amg);                           /* the operator changes only when everything is in order */
    op->amg = s;
    return 0;
+}
+
+extern "C" int primme_amd_operator_set_amg(primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smooth_steps, int coarse_steps, double theta, double over, double shift) {
+   return amg_configure(op, rowptr_host, colind_host, values_host, smooth_steps, coarse_steps, theta, over, 0.0, shift);
+}
+
+extern "C" int primme_amd_operator_set_amg_smoothed(primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smooth_steps, int coarse_steps, double theta, double omega, double shift) {
+   if (!(omega > 0.0 && omega < 2.0)) return -1;
+   return amg_configure(op, rowptr_host, colind_host, values_host, smooth_steps, coarse_steps, theta, 1.0, omega, shift);
 }
 
 struct amg_run {
@@ -751,9 +785,18 @@ static void amg_vcycle(amg_run *r, int l, const char *b, int64_t lb, char *const
    const int64_t ldc = s->lv[l + 1].ld, LYc[2] = {ldc, ldc};
    char *bc = amg_panel(s, r->es, l + 1, 0), *Wc = amg_panel(s, r->es, l + 1, 3);
    char *const Yc[2] = {amg_panel(s, r->es, l + 1, 1), amg_panel(s, r->es, l + 1, 2)};
-   if (!r->rc) { r->rc = hipk_amg_restrict(r->stream, r->dt, L->n, L->nc, L->aggptr, L->aggrows, r->nc, W, ldw, bc, ldc); g_amg_launches++; }
+   /* smoothed aggregation: R_l = P_l' and P_l in CSR; plain aggregation: the aggregate maps */
+   if (!r->rc) {
+      r->rc = L->rrp ? hipk_amg_csr_apply(r->stream, r->dt, L->nc, L->n, L->rrp, L->rci, L->rva, 0, r->nc, W, ldw, bc, ldc)
+                     : hipk_amg_restrict(r->stream, r->dt, L->n, L->nc, L->aggptr, L->aggrows, r->nc, W, ldw, bc, ldc);
+      g_amg_launches++;
+   }
    amg_vcycle(r, l + 1, bc, ldc, Yc, LYc, Wc, ldc);
-   if (!r->rc) { r->rc = hipk_amg_prolong_add(r->stream, r->dt, L->n, L->nc, L->agg, s->over, r->nc, Yc[0], ldc, Y[a], LY[a]); g_amg_launches++; }
+   if (!r->rc) {
+      r->rc = L->prp ? hipk_amg_csr_apply(r->stream, r->dt, L->n, L->nc, L->prp, L->pci, L->pva, 1, r->nc, Yc[0], ldc, Y[a], LY[a])
+                     : hipk_amg_prolong_add(r->stream, r->dt, L->n, L->nc, L->agg, s->over, r->nc, Yc[0], ldc, Y[a], LY[a]);
+      g_amg_launches++;
+   }
    (void)amg_cheb(r, l, s->nu, b, lb, Y, LY, W, ldw, a, 0);
 }
 

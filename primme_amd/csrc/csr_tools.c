@@ -9,6 +9,7 @@
  *   primme_amd_csr_tile_plan      the row tiles, column windows and 16-bit index stream of the device CSR operator
  *   primme_amd_mg_plan            the grids and weights of the geometric multigrid preconditioner (primme_amd.h)
  *   primme_amd_amg_plan_create    the aggregates and Galerkin matrices of the algebraic multigrid preconditioner
+ *   primme_amd_amg_plan_create_smoothed   the same with smoothed prolongations and a general triple product
  *
  * Indices are 0-based int32 (the device kernels' format); values are double, complex as
  * (re, im) pairs.  Everything returned is malloc'ed; release with primme_amd_host_free. */
@@ -475,7 +476,11 @@ static void amg_level_free(primme_amd_amg_level *L) {
 }
 void primme_amd_amg_plan_free(primme_amd_amg_plan *plan) {
    if (!plan) return;
-   for (int l = 0; l < PRIMME_AMD_AMG_MAXLEVELS; l++) amg_level_free(&plan->level[l]);
+   for (int l = 0; l < PRIMME_AMD_AMG_MAXLEVELS; l++) {
+      primme_amd_amg_transfer *X = &plan->transfer[l];
+      amg_level_free(&plan->level[l]);
+      free(X->prowptr); free(X->pcolind); free(X->pvalues); free(X->rrowptr); free(X->rcolind); free(X->rvalues);
+   }
    free(plan);
 }
 static int amg_i32_cmp(const void *a, const void *b) {
@@ -592,8 +597,143 @@ static int amg_galerkin(const primme_amd_amg_level *F, primme_amd_amg_level *Cl)
    return 0;
 }
 
-int primme_amd_amg_plan_create(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
-      double shift, double theta, primme_amd_amg_plan **plan) {
+/* P = (I - (omega / rho) D^-1 M) T for the aggregates of F (nc, agg set; dinv and rho too) and its transpose R.  Row i of P:
+ * the sums s_J of m_iq over the entries q with agg[col q] = J, in the row's order, then p_iJ = [J = agg[i]] - (omega / rho)
+ * dinv_i s_J; columns sorted, one entry per position, an entry that cancels to zero stays.  R by a counting sort over the
+ * columns of P: rows of R have ascending column indices and the bits of P. */
+static int amg_prolongation(const primme_amd_amg_level *F, double omega, primme_amd_amg_transfer *X) {
+   const int64_t n = F->n, nc = F->nc;
+   const double w = omega / F->rho;
+   int rc = 0;
+   X->prowptr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+   X->pcolind = (int32_t *)malloc(sizeof(int32_t) * (size_t)(F->nnz + n));      /* a row of P has at most the row of M and agg[i] */
+   X->pvalues = (double *)malloc(sizeof(double) * (size_t)(F->nnz + n));
+   X->rrowptr = (int32_t *)calloc((size_t)(nc + 1), sizeof(int32_t));
+   int32_t *mark = (int32_t *)malloc(sizeof(int32_t) * (size_t)nc), *list = (int32_t *)malloc(sizeof(int32_t) * (size_t)nc);
+   double *acc = (double *)malloc(sizeof(double) * (size_t)nc);
+   if (!X->prowptr || !X->pcolind || !X->pvalues || !X->rrowptr || !mark || !list || !acc) rc = -5;
+   int64_t nnz = 0;
+   if (!rc) {
+      for (int64_t J = 0; J < nc; J++) mark[J] = -1;
+      X->prowptr[0] = 0;
+   }
+   for (int64_t i = 0; i < n && !rc; i++) {
+      const int32_t own = F->agg[i];
+      int32_t cnt = 0;
+      mark[own] = (int32_t)i; acc[own] = 0.0; list[cnt++] = own;
+      for (int32_t q = F->rowptr[i]; q < F->rowptr[i + 1]; q++) {
+         const int32_t J = F->agg[F->colind[q]];
+         if (mark[J] != (int32_t)i) { mark[J] = (int32_t)i; acc[J] = F->values[q]; list[cnt++] = J; }
+         else acc[J] += F->values[q];
+      }
+      if (nnz + cnt > INT32_MAX) { rc = -4; break; }
+      qsort(list, (size_t)cnt, sizeof(int32_t), amg_i32_cmp);
+      const double c = w * F->dinv[i];
+      for (int32_t k = 0; k < cnt; k++) {
+         const int32_t J = list[k];
+         X->pcolind[nnz] = J;
+         X->pvalues[nnz] = (J == own ? 1.0 : 0.0) - c * acc[J];
+         X->rrowptr[J + 1]++;
+         nnz++;
+      }
+      X->prowptr[i + 1] = (int32_t)nnz;
+   }
+   free(mark); free(list); free(acc);
+   if (rc) return rc;
+   X->pnnz = nnz;
+   X->rcolind = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1));
+   X->rvalues = (double *)malloc(sizeof(double) * (size_t)(nnz > 0 ? nnz : 1));
+   int32_t *cur = (int32_t *)malloc(sizeof(int32_t) * (size_t)nc);
+   if (!X->rcolind || !X->rvalues || !cur) { free(cur); return -5; }
+   for (int64_t J = 0; J < nc; J++) { X->rrowptr[J + 1] += X->rrowptr[J]; cur[J] = X->rrowptr[J]; }
+   for (int64_t i = 0; i < n; i++)
+      for (int32_t p = X->prowptr[i]; p < X->prowptr[i + 1]; p++) {
+         const int32_t at = cur[X->pcolind[p]]++;
+         X->rcolind[at] = (int32_t)i; X->rvalues[at] = X->pvalues[p];
+      }
+   free(cur);
+   return 0;
+}
+
+/* C = R F P for the transfer matrices X of F (R = P').  Row I of the upper triangle: over the entries (i, r) of row I of R
+ * in their order, the entries (k, m) of row i of F in theirs and the entries (J, p) of row k of P with J >= I in theirs,
+ * c_IJ += (r m) p; columns sorted, one entry per position.  Entry (J, I) then takes the bits of (I, J): C is exactly
+ * symmetric.  -4 when C would have more than INT32_MAX entries. */
+static int amg_galerkin_general(const primme_amd_amg_level *F, const primme_amd_amg_transfer *X, primme_amd_amg_level *Cl) {
+   const int64_t nc = F->nc;
+   int rc = 0;
+   int64_t cap = F->nnz > 16 ? F->nnz : 16, unnz = 0;
+   int32_t *urp = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nc + 1)), *uci = (int32_t *)malloc(sizeof(int32_t) * (size_t)cap);
+   double *uva = (double *)malloc(sizeof(double) * (size_t)cap);
+   int32_t *mark = (int32_t *)malloc(sizeof(int32_t) * (size_t)nc), *list = (int32_t *)malloc(sizeof(int32_t) * (size_t)nc);
+   int32_t *cnt = (int32_t *)calloc((size_t)(nc + 1), sizeof(int32_t));
+   double *acc = (double *)malloc(sizeof(double) * (size_t)nc);
+   if (!urp || !uci || !uva || !mark || !list || !cnt || !acc) rc = -5;
+   if (!rc) {
+      for (int64_t J = 0; J < nc; J++) mark[J] = -1;
+      urp[0] = 0;
+   }
+   int64_t total = 0;
+   for (int64_t I = 0; I < nc && !rc; I++) {
+      int32_t len = 0;
+      for (int32_t a = X->rrowptr[I]; a < X->rrowptr[I + 1]; a++) {
+         const int32_t i = X->rcolind[a];
+         const double r = X->rvalues[a];
+         for (int32_t q = F->rowptr[i]; q < F->rowptr[i + 1]; q++) {
+            const int32_t k = F->colind[q];
+            const double rm = r * F->values[q];
+            for (int32_t t = X->prowptr[k]; t < X->prowptr[k + 1]; t++) {
+               const int32_t J = X->pcolind[t];
+               if (J < (int32_t)I) continue;
+               if (mark[J] != (int32_t)I) { mark[J] = (int32_t)I; acc[J] = rm * X->pvalues[t]; list[len++] = J; }
+               else acc[J] += rm * X->pvalues[t];
+            }
+         }
+      }
+      if (unnz + len > cap) {
+         while (unnz + len > cap) cap *= 2;
+         int32_t *nci = (int32_t *)realloc(uci, sizeof(int32_t) * (size_t)cap);
+         if (nci) uci = nci;
+         double *nva = (double *)realloc(uva, sizeof(double) * (size_t)cap);
+         if (nva) uva = nva;
+         if (!nci || !nva) { rc = -5; break; }
+      }
+      qsort(list, (size_t)len, sizeof(int32_t), amg_i32_cmp);
+      for (int32_t k = 0; k < len; k++) {
+         const int32_t J = list[k];
+         uci[unnz] = J; uva[unnz] = acc[J]; unnz++;
+         cnt[I]++;
+         if (J != (int32_t)I) cnt[J]++;
+      }
+      total += 2 * (int64_t)len - (len > 0 && list[0] == (int32_t)I ? 1 : 0);
+      if (unnz > INT32_MAX || total > INT32_MAX) { rc = -4; break; }
+      urp[I + 1] = (int32_t)unnz;
+   }
+   free(mark); free(list); free(acc);
+   if (!rc) {
+      Cl->n = nc; Cl->nnz = total;
+      Cl->rowptr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nc + 1));
+      Cl->colind = (int32_t *)malloc(sizeof(int32_t) * (size_t)(total > 0 ? total : 1));
+      Cl->values = (double *)malloc(sizeof(double) * (size_t)(total > 0 ? total : 1));
+      if (!Cl->rowptr || !Cl->colind || !Cl->values) rc = -5;
+   }
+   if (!rc) {
+      Cl->rowptr[0] = 0;
+      for (int64_t I = 0; I < nc; I++) { Cl->rowptr[I + 1] = Cl->rowptr[I] + cnt[I]; cnt[I] = Cl->rowptr[I]; }
+      /* rows ascending: when row I is reached, its entries left of the diagonal are in place */
+      for (int64_t I = 0; I < nc; I++)
+         for (int32_t u = urp[I]; u < urp[I + 1]; u++) {
+            const int32_t J = uci[u];
+            Cl->colind[cnt[I]] = J; Cl->values[cnt[I]] = uva[u]; cnt[I]++;
+            if (J != (int32_t)I) { Cl->colind[cnt[J]] = (int32_t)I; Cl->values[cnt[J]] = uva[u]; cnt[J]++; }
+         }
+   }
+   free(urp); free(uci); free(uva); free(cnt);
+   return rc;
+}
+
+static int amg_plan_build(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
+      double shift, double theta, double omega, primme_amd_amg_plan **plan) {
    if (!plan) return -1;
    *plan = NULL;
    if (n < 1 || !rowptr || !colind || !values || (elem_size != 8 && elem_size != 4) || !(shift >= 0.0) || !(theta >= 0.0 && theta < 1.0)) return -1;
@@ -605,7 +745,7 @@ int primme_amd_amg_plan_create(int64_t n, const int32_t *rowptr, const int32_t *
    if (!rc) {
       primme_amd_amg_level *L = &P->level[0];
       const int64_t nnz = rowptr[n];
-      P->shift = shift; P->theta = theta;
+      P->shift = shift; P->theta = theta; P->omega = omega;
       L->n = n; L->nnz = nnz;
       L->rowptr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
       L->colind = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1));
@@ -644,7 +784,11 @@ int primme_amd_amg_plan_create(int64_t n, const int32_t *rowptr, const int32_t *
       for (int64_t j = 0; j < nc; j++) L->aggptr[j + 1] += L->aggptr[j];
       for (int64_t j = 0; j < nc; j++) tmp[j] = L->aggptr[j];
       for (int64_t i = 0; i < L->n; i++) L->aggrows[tmp[agg[i]]++] = (int32_t)i;
-      rc = amg_galerkin(L, &P->level[l + 1]);
+      if (omega == 0.0) rc = amg_galerkin(L, &P->level[l + 1]);
+      else {
+         rc = amg_prolongation(L, omega, &P->transfer[l]);
+         if (!rc) rc = amg_galerkin_general(L, &P->transfer[l], &P->level[l + 1]);
+      }
       if (!rc) rc = amg_level_finish(&P->level[l + 1], dg);
       l++;
    }
@@ -653,6 +797,19 @@ int primme_amd_amg_plan_create(int64_t n, const int32_t *rowptr, const int32_t *
    P->nlevels = l + 1;
    *plan = P;
    return 0;
+}
+
+int primme_amd_amg_plan_create(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
+      double shift, double theta, primme_amd_amg_plan **plan) {
+   return amg_plan_build(n, rowptr, colind, values, elem_size, shift, theta, 0.0, plan);
+}
+
+int primme_amd_amg_plan_create_smoothed(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size,
+      double shift, double theta, double omega, primme_amd_amg_plan **plan) {
+   if (!plan) return -1;
+   *plan = NULL;
+   if (!(omega > 0.0 && omega < 2.0)) return -1;
+   return amg_plan_build(n, rowptr, colind, values, elem_size, shift, theta, omega, plan);
 }
 
 int primme_amd_amg_coarse_inverse(const primme_amd_amg_plan *plan, double *G) {

@@ -1,12 +1,14 @@
 /* hipk_amg.hip — device pieces of the aggregation algebraic multigrid preconditioner for CSR operators (gfx950).
  *
  * One V-cycle (primme_amd_amg_precond in amd_operator.hip; DESIGN.md, "Aggregation algebraic multigrid preconditioner") runs
- * the level operators through hipk_csr_matvec and, between the products, four passes over panels of vectors:
+ * the level operators through hipk_csr_matvec and, between the products, these passes over panels of vectors:
  *   amg_update_kernel    Out = cy Yk + cp Yprev + dinv o (cx X + cw W): a step of the Chebyshev iteration for D^-1 M_l with
  *                        W = M_l Yk, or (dinv = NULL, cx = 1, cw = -1) the residual; row-local
  *   amg_restrict_kernel  C[j] = sum of F over the rows of aggregate j (P' F for the 0/1 matrix P of the aggregate map)
  *   amg_prolong_kernel   Y[i] += over C[agg[i]]  (Y += over P C)
  *   amg_dense_kernel     Y = G X for the dense inverse G of the last level, at most PRIMME_AMD_AMG_DENSE_ROWS rows
+ *   amg_csr_kernel       Out = T In or Out += T In for a CSR matrix T with double values: the restriction (T = P') and the
+ *                        interpolation (T = P) of smoothed aggregation, where P has several entries per row
  * A lane owns VW consecutive elements of the streamed panel (VW = 16 bytes when base and leading dimension of every streamed
  * panel allow it, one element where not); what is indexed through a map (the rows of an aggregate, the aggregate of a row) is
  * an element load.  Arithmetic in double whatever T is, one rounding per stored element.  No atomics: every sum has one
@@ -146,6 +148,63 @@ amg_prolong_kernel(int64_t nf, double over, const int32_t *__restrict__ agg, con
    for (int64_t i = nv * VW + gid; i < nf; i += stride) y[i] = (T)fma(over, (double)cc[agg[i]], (double)y[i]);
 }
 
+/* Out = T In (ACC = 0) or Out += T In (ACC = 1) for a CSR matrix T with double values: the transfers of smoothed aggregation,
+ * T = R_l = P_l' (restriction) and T = P_l (interpolation).  The rows are dealt as amg_restrict_kernel deals the aggregates:
+ * a wave takes 64 VW consecutive rows per trip, lane l the VW from base + l VW on; a row of at most AMG_LANE_ROWS entries is
+ * summed by its lane, positions ascending, a longer one by the whole wave, lane l the positions first + l, first + l + 64, ...
+ * and the 64 partial sums folded by the xor butterfly.  The sum is in double; with ACC the lane's VW elements of Out are
+ * loaded in one access, added in double, and the result rounded once.  Wave-uniform trip and long-row loops. */
+template <typename T, int VW, int ACC>
+__global__ void __launch_bounds__(HIPK_BLOCK)
+amg_csr_kernel(int64_t nrows, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colind, const double *__restrict__ values,
+      const T *In, int64_t ldin, T *Out, int64_t ldout) {
+   typedef amg_pack<T, VW> P;
+   const T *__restrict__ in = In + (size_t)blockIdx.y * ldin;
+   T *out = Out + (size_t)blockIdx.y * ldout;
+   const int lane = threadIdx.x & (HIPK_WAVE - 1);
+   const int64_t nwaves = (int64_t)gridDim.x * (HIPK_BLOCK / HIPK_WAVE);
+   const int64_t wave = (int64_t)blockIdx.x * (HIPK_BLOCK / HIPK_WAVE) + (threadIdx.x / HIPK_WAVE);
+   const int64_t per = (int64_t)HIPK_WAVE * VW;
+   for (int64_t base = wave * per; base < nrows; base += nwaves * per) {
+      const int64_t j0 = base + (int64_t)lane * VW;
+      double s[VW];
+      int32_t p0[VW], p1[VW];
+#pragma unroll
+      for (int e = 0; e < VW; e++) {
+         const int64_t j = j0 + e;
+         p0[e] = p1[e] = 0;
+         if (j < nrows) { p0[e] = rowptr[j]; p1[e] = rowptr[j + 1]; }
+         s[e] = 0.0;
+         if (p1[e] - p0[e] <= AMG_LANE_ROWS)
+            for (int32_t p = p0[e]; p < p1[e]; p++) s[e] = fma(values[p], (double)in[colind[p]], s[e]);
+      }
+#pragma unroll
+      for (int e = 0; e < VW; e++) {
+         unsigned long long mask = __ballot(p1[e] - p0[e] > AMG_LANE_ROWS);
+         while (mask) {
+            const int src = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const int32_t q0 = __shfl(p0[e], src), q1 = __shfl(p1[e], src);
+            double t = 0.0;
+            for (int32_t p = q0 + lane; p < q1; p += HIPK_WAVE) t = fma(values[p], (double)in[colind[p]], t);
+            for (int o = HIPK_WAVE / 2; o > 0; o >>= 1) t += __shfl_xor(t, o);
+            if (lane == src) s[e] = t;
+         }
+      }
+      if (VW > 1 && j0 + VW <= nrows) {
+         P po;
+         if (ACC) po = *(const P *)(out + j0);
+#pragma unroll
+         for (int e = 0; e < VW; e++) po.v[e] = (T)(ACC ? s[e] + (double)po.v[e] : s[e]);
+         *(P *)(out + j0) = po;
+      } else {
+#pragma unroll
+         for (int e = 0; e < VW; e++)
+            if (j0 + e < nrows) out[j0 + e] = (T)(ACC ? s[e] + (double)out[j0 + e] : s[e]);
+      }
+   }
+}
+
 /* one workgroup per column: the column of X in LDS, thread i row i of G X with the terms added in ascending order of the
  * column index; G is symmetric, so its row i is read as column i and consecutive threads read consecutive addresses */
 template <typename T>
@@ -234,6 +293,27 @@ extern "C" int hipk_amg_prolong_add(void *hip_stream, hipk_dtype dt, int64_t nf,
       const dim3 grid(amg_grid(nf, (int64_t)HIPK_BLOCK * (vec ? VW : 1)), nx);
       if (vec) hipLaunchKernelGGL((amg_prolong_kernel<T, VW>), grid, dim3(HIPK_BLOCK), 0, st, nf, over, agg, (const T *)C, ldc, (T *)Y, ldy);
       else hipLaunchKernelGGL((amg_prolong_kernel<T, 1>), grid, dim3(HIPK_BLOCK), 0, st, nf, over, agg, (const T *)C, ldc, (T *)Y, ldy);
+   });
+   HIPK_CHECK(hipGetLastError());
+   return 0;
+}
+
+extern "C" int hipk_amg_csr_apply(void *hip_stream, hipk_dtype dt, int64_t nrows, int64_t ncols, const int32_t *rowptr, const int32_t *colind,
+      const double *values, int accumulate, int nx, const void *In, int64_t ldin, void *Out, int64_t ldout) {
+   if (dt != HIPK_F64 && dt != HIPK_F32) return -44;
+   if (nx <= 0) return 0;
+   if (nrows < 1 || ncols < 1 || nrows > INT32_MAX || ncols > INT32_MAX || nx > HIPK_CHEB_MAXCOLS || !rowptr || !colind || !values ||
+       !In || !Out || In == Out) return -1;
+   hipStream_t st = (hipStream_t)hip_stream;
+   hipk_prof_scope ps_(HIPK_PROF_VEC, st, hipk_stream_bytes(dt, (accumulate ? 2 : 1) * nrows + ncols, (double)nx) + 4.0 * nrows * nx);
+   DISPATCH_RT(dt, {
+      constexpr int VW = 16 / sizeof(T);
+      const bool vec = amg_al16(Out, ldout, sizeof(T));            /* the stored panel; In is read through the column indices */
+      const dim3 grid(amg_grid(nrows, (int64_t)HIPK_BLOCK * (vec ? VW : 1)), nx);
+      if (vec && accumulate) hipLaunchKernelGGL((amg_csr_kernel<T, VW, 1>), grid, dim3(HIPK_BLOCK), 0, st, nrows, rowptr, colind, values, (const T *)In, ldin, (T *)Out, ldout);
+      else if (vec) hipLaunchKernelGGL((amg_csr_kernel<T, VW, 0>), grid, dim3(HIPK_BLOCK), 0, st, nrows, rowptr, colind, values, (const T *)In, ldin, (T *)Out, ldout);
+      else if (accumulate) hipLaunchKernelGGL((amg_csr_kernel<T, 1, 1>), grid, dim3(HIPK_BLOCK), 0, st, nrows, rowptr, colind, values, (const T *)In, ldin, (T *)Out, ldout);
+      else hipLaunchKernelGGL((amg_csr_kernel<T, 1, 0>), grid, dim3(HIPK_BLOCK), 0, st, nrows, rowptr, colind, values, (const T *)In, ldin, (T *)Out, ldout);
    });
    HIPK_CHECK(hipGetLastError());
    return 0;

@@ -7,12 +7,13 @@ per invocation, so that a job runs each under a time limit of its own and chains
     python scripts/amg_headline.py --case lap   --config chebyshev
     python scripts/amg_headline.py --case lap   --config multigrid
     python scripts/amg_headline.py --case lap   --config amg
+    python scripts/amg_headline.py --case lap   --config amg_smoothed # smoothed aggregation; also for --case lunda
 
 Every invocation adds (or replaces) its row in profiles/amg_headline.json (--out): the seconds of each of --repeats solves
 after a short warm-up solve of the same configuration, their median, outer iterations, matvecs, the preconditioner's counters
 and the largest eigenvalue error against the truth.  The amg rows also hold the set-up seconds on the host (one call of
-primme_amd_amg_plan_create on the same arrays, timed by itself), the rows of the levels and the operator complexity
-sum nnz(M_l) / nnz(M_0).
+primme_amd_amg_plan_create or _create_smoothed on the same arrays, timed by itself), the rows of the levels and the operator
+complexity sum nnz(M_l) / nnz(M_0).
 
 Cases
   lunda  BASELINE configs[2]: LUNDA.mtx tiled block-diagonally 34 014 times (tile t scaled by 1 + t/T, n = 5 000 058), 20
@@ -45,15 +46,20 @@ class Plan(C.Structure):
     _fields_ = [("nlevels", C.c_int), ("shift", C.c_double), ("theta", C.c_double), ("level", Level * 24)]
 
 
-def host_setup(lib, rp, ci, va, shift=0.0, theta=0.08):
-    """(seconds of primme_amd_amg_plan_create, rows per level, operator complexity)"""
+def host_setup(lib, rp, ci, va, shift=0.0, theta=0.08, omega=None):
+    """(seconds of primme_amd_amg_plan_create, or of _create_smoothed with omega, rows per level, operator complexity)"""
+    lib.primme_amd_amg_plan_create_smoothed.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double,
+                                                        C.c_double, C.POINTER(C.POINTER(Plan))]
     lib.primme_amd_amg_plan_create.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double,
                                                C.POINTER(C.POINTER(Plan))]
     lib.primme_amd_amg_plan_free.argtypes = [C.POINTER(Plan)]
     rp, ci, va = (np.ascontiguousarray(a, dtype=t) for a, t in ((rp, np.int32), (ci, np.int32), (va, np.float64)))
     P = C.POINTER(Plan)()
     t0 = time.perf_counter()
-    rc = lib.primme_amd_amg_plan_create(len(rp) - 1, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, 8, shift, theta, C.byref(P))
+    if omega is None:
+        rc = lib.primme_amd_amg_plan_create(len(rp) - 1, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, 8, shift, theta, C.byref(P))
+    else:
+        rc = lib.primme_amd_amg_plan_create_smoothed(len(rp) - 1, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, 8, shift, theta, omega, C.byref(P))
     secs = time.perf_counter() - t0
     assert rc == 0, rc
     lv = [P.contents.level[l] for l in range(P.contents.nlevels)]
@@ -65,7 +71,7 @@ def host_setup(lib, rp, ci, va, shift=0.0, theta=0.08):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", choices=("lunda", "lap"), required=True)
-    ap.add_argument("--config", choices=("none", "jacobi", "chebyshev", "multigrid", "amg"), required=True)
+    ap.add_argument("--config", choices=("none", "jacobi", "chebyshev", "multigrid", "amg", "amg_smoothed"), required=True)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--max-outer", type=int, default=60000)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "amg_headline.json"))
@@ -86,7 +92,8 @@ def main():
         kw = dict(numEvals=20, target="closest_abs", targetShifts=[shift], method="JDQMR", maxBlockSize=8, eps=1e-8, aNorm=aN,
                   return_evecs=False)
         workload = f"configs[2]: LUNDA.mtx tiled {T}x (n = {n}), 20 eigenvalues closest to {shift:.4e}, JDQMR, block 8, eps 1e-8 |A|"
-        allowed = {"jacobi": ("jacobi K = diag(A) - shift", ("jacobi", shift)), "amg": ("amg V(2,2)", ("amg",))}
+        allowed = {"jacobi": ("jacobi K = diag(A) - shift", ("jacobi", shift)), "amg": ("amg V(2,2)", ("amg",)),
+                   "amg_smoothed": ("amg smoothed V(2,2)", ("amg_smoothed",))}
     else:
         dims, aN = ((316, 317) if a.small else (3162, 3163)), 8.0
         rp, ci, va, n = problems.laplacian_csr(dims)
@@ -94,7 +101,7 @@ def main():
         kw = dict(numEvals=10, target="smallest", method="GD_plusK", eps=1e-8, aNorm=aN, v0=problems.start_vector(n), return_evecs=False)
         workload = f"CSR 5-point Laplacian {dims[0]} x {dims[1]}, 10 smallest, GD+k, block 1, eps 1e-8 |A|"
         allowed = {"none": ("none", None), "chebyshev": ("chebyshev steps=16", "chebyshev"), "multigrid": ("multigrid V(2,2)", ("multigrid", dims, 2, 16)),
-                   "amg": ("amg V(2,2)", ("amg",))}
+                   "amg": ("amg V(2,2)", ("amg",)), "amg_smoothed": ("amg smoothed V(2,2)", ("amg_smoothed",))}
     if a.config not in allowed:
         raise SystemExit(f"case {a.case} has the configurations {sorted(allowed)}")
     doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
@@ -108,8 +115,8 @@ def main():
         precond = ("chebyshev", 16, float(th[-1] + (th[-1] - th[0]) / 10))
     row = dict(label=label, precond=[list(v) if isinstance(v, tuple) else v for v in precond] if isinstance(precond, tuple) else precond,
                command=" ".join(["python", "scripts/amg_headline.py"] + sys.argv[1:]))
-    if a.config == "amg":
-        secs, lrows, cx = host_setup(lib, rp, ci, va)
+    if a.config in ("amg", "amg_smoothed"):
+        secs, lrows, cx = host_setup(lib, rp, ci, va, omega=4.0 / 3.0 if a.config == "amg_smoothed" else None)
         row.update(setup_seconds_host=secs, level_rows=lrows, levels=len(lrows), operator_complexity=cx)
         print(json.dumps(row), flush=True)
     kw["maxOuterIterations"] = a.max_outer
