@@ -407,8 +407,9 @@ template <bool PM>
 static int launch_finalize(hipk_ctx *ctx, const double *partials, int nblocks, int pstride, int nout, double *out_dev) {
    if (nout <= 0) return 0;
    const hipk_xr_dev xr = hipk_xr_take(ctx, out_dev, nout);
-   double *mh = hipk_mirror_of(ctx, out_dev);
-   const hipk_fin_flag ff = hipk_next_flag(ctx, out_dev);
+   /* the kernel stores nout results: mirrored (and flagged) only when all of them lie inside the mirror */
+   double *mh = hipk_mirror_of(ctx, out_dev, (size_t)nout);
+   const hipk_fin_flag ff = hipk_next_flag(ctx, out_dev, (size_t)nout);
    if (xr.tab)
       hipLaunchKernelGGL((hipk_finalize_kernel<PM, true>), dim3(nout), dim3(fin_block_for(nblocks)), 0, ctx->stream,
             partials, nblocks, nout, pstride, out_dev, mh, ff, xr);

@@ -118,8 +118,13 @@ static inline hipk_xr_dev hipk_xr_take(hipk_ctx *ctx, const double *out_dev, int
    return hipk_xr_make(ctx->xr);
 }
 
-static inline double *hipk_mirror_of(const hipk_ctx *ctx, const double *out_dev) {
-   if (ctx->mirror_dev && out_dev >= ctx->mirror_dev && out_dev < ctx->mirror_dev + ctx->mirror_count)
+/* the pinned copy of [out_dev, out_dev + count), or NULL when that range is not WHOLLY inside the declared mirror
+ * [mirror_dev, mirror_dev + mirror_count): a launch that stores `count` results passes its count, so that a range which
+ * starts inside the mirror and ends past it is treated as not mirrored (no host store, no flag) instead of being stored
+ * past the declared end of the pinned array */
+static inline double *hipk_mirror_of(const hipk_ctx *ctx, const double *out_dev, size_t count = 1) {
+   if (ctx->mirror_dev && count > 0 && out_dev >= ctx->mirror_dev && out_dev < ctx->mirror_dev + ctx->mirror_count &&
+         count <= (size_t)(ctx->mirror_dev + ctx->mirror_count - out_dev))
       return ctx->mirror_host + (out_dev - ctx->mirror_dev);
    return NULL;
 }
@@ -154,11 +159,11 @@ struct hipk_prof_scope {
 
 /* arguments every finalize kernel takes for the completion flag (all NULL / 0: no flag) */
 struct hipk_fin_flag { unsigned long long *flag; unsigned int *counter; unsigned long long seq; };
-/* next sequence number for a finalize launch whose output lies in the mirror (else an empty record) */
-static inline hipk_fin_flag hipk_next_flag(hipk_ctx *ctx, const double *out_dev) {
+/* next sequence number for a finalize launch whose `count` outputs lie in the mirror (else an empty record) */
+static inline hipk_fin_flag hipk_next_flag(hipk_ctx *ctx, const double *out_dev, size_t count = 1) {
    hipk_fin_flag f = {NULL, NULL, 0};
    if (ctx->skip_flag_once) { ctx->skip_flag_once = 0; ctx->need_sync = 1; return f; }
-   if (ctx->flag_dev && hipk_mirror_of(ctx, out_dev)) { f.flag = ctx->flag_dev; f.counter = ctx->fin_counter; f.seq = ++ctx->seq_issued; ctx->need_sync = 0; }
+   if (ctx->flag_dev && hipk_mirror_of(ctx, out_dev, count)) { f.flag = ctx->flag_dev; f.counter = ctx->fin_counter; f.seq = ++ctx->seq_issued; ctx->need_sync = 0; }
    else ctx->need_sync = 1;      /* a reduction whose results the flag does not cover */
    return f;
 }
@@ -196,7 +201,7 @@ int hipk_reserve_partials(hipk_ctx *ctx, size_t n);
 static inline hipk_fin_args hipk_make_fin(hipk_ctx *ctx, double *out_dev, int kind, int nblocks, int nout) {
    hipk_fin_args fa;
    memset(&fa, 0, sizeof(fa));
-   fa.out = out_dev; fa.out_host = hipk_mirror_of(ctx, out_dev); fa.arrive = ctx->arrive_counter;
+   fa.out = out_dev; fa.out_host = hipk_mirror_of(ctx, out_dev, nout > 0 ? (size_t)nout : 1); fa.arrive = ctx->arrive_counter;
    fa.enabled = (hipk_inkernel_fin_mask() & kind) && ctx->arrive_counter != NULL && nblocks > 0 && nout > 0;
    if (fa.enabled) {
       int g = 8;
@@ -205,7 +210,7 @@ static inline hipk_fin_args hipk_make_fin(hipk_ctx *ctx, double *out_dev, int ki
       if (hipk_reserve_partials(ctx, (size_t)nblocks * nout + (size_t)nout * HIPK_FIN_MAXGROUPS)) { fa.enabled = 0; return fa; }
       fa.group = ctx->partials + (size_t)nblocks * nout;
       fa.xr = hipk_xr_take(ctx, out_dev, nout);
-      fa.flag = hipk_next_flag(ctx, out_dev);
+      fa.flag = hipk_next_flag(ctx, out_dev, (size_t)nout);
    }
    return fa;
 }

@@ -352,8 +352,9 @@ static int panel_dots_t(hipk_ctx *ctx, int64_t m, const SegArgs &sa, const T *X,
    else dots_launch<T, 1>(ctx, grid, nxt, sa, X, ldX, nx, m);
    hipk_prof_end(pslot, ctx->stream);
    HIPK_CHECK(hipGetLastError());
+   const size_t span = (size_t)ldout * (nx - 1) + sa.total;      /* from the first result to the last one stored */
    hipLaunchKernelGGL(finalize_ld_kernel, dim3((unsigned)nout), dim3(HIPK_BLOCK), 0, ctx->stream,
-         ctx->partials, gx, (int)nout, sa.total, ldout, out_dev, hipk_mirror_of(ctx, out_dev), hipk_next_flag(ctx, out_dev));
+         ctx->partials, gx, (int)nout, sa.total, ldout, out_dev, hipk_mirror_of(ctx, out_dev, span), hipk_next_flag(ctx, out_dev, span));
    HIPK_CHECK(hipGetLastError());
    return 0;
 }

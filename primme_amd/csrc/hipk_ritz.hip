@@ -949,7 +949,7 @@ rr_arrow_kernel(hipk_rr_in in, const double *__restrict__ fov, int nfov, const d
 extern "C" int hipk_rr_arrow(hipk_ctx *ctx, const hipk_rr_in *in, const double *fov_dev, int nfov, const double *alpha_dev, double *out_dev) {
    if (!in || in->k < 1 || in->k > 16 || in->L < 0 || in->L > 10) return -1;
    if (nfov > 126) return -1;
-   hipLaunchKernelGGL(rr_arrow_kernel, dim3(1), dim3(64), 0, ctx->stream, *in, fov_dev, nfov, alpha_dev, out_dev, hipk_mirror_of(ctx, out_dev));
+   hipLaunchKernelGGL(rr_arrow_kernel, dim3(1), dim3(64), 0, ctx->stream, *in, fov_dev, nfov, alpha_dev, out_dev, hipk_mirror_of(ctx, out_dev, 34));      /* rr_arrow_solve stores out_host[0 .. 33] */
    HIPK_CHECK(hipGetLastError());
    return 0;
 }
@@ -1032,10 +1032,10 @@ extern "C" int hipk_tail_finish(hipk_ctx *ctx, const hipk_rr_in *in, const doubl
    if (!in) memset(&none, 0, sizeof(none));
    if (xr.tab)
       hipLaunchKernelGGL((tail_finish_kernel<true>), dim3(1), dim3(nt), 0, ctx->stream, ctx->tailp, np2, ctx->partials, np3, n2o, np2 > 0 ? hipk_mirror_of(ctx, n2o) : NULL,
-            doto, hipk_mirror_of(ctx, doto), ff, xr, in ? 1 : 0, in ? *in : none, fov_dev, nfov, hnext_out, in ? hipk_mirror_of(ctx, hnext_out) : NULL);
+            doto, hipk_mirror_of(ctx, doto), ff, xr, in ? 1 : 0, in ? *in : none, fov_dev, nfov, hnext_out, in ? hipk_mirror_of(ctx, hnext_out, 34) : NULL);
    else
       hipLaunchKernelGGL((tail_finish_kernel<false>), dim3(1), dim3(nt), 0, ctx->stream, ctx->tailp, np2, ctx->partials, np3, n2o, np2 > 0 ? hipk_mirror_of(ctx, n2o) : NULL,
-            doto, hipk_mirror_of(ctx, doto), ff, xr, in ? 1 : 0, in ? *in : none, fov_dev, nfov, hnext_out, in ? hipk_mirror_of(ctx, hnext_out) : NULL);
+            doto, hipk_mirror_of(ctx, doto), ff, xr, in ? 1 : 0, in ? *in : none, fov_dev, nfov, hnext_out, in ? hipk_mirror_of(ctx, hnext_out, 34) : NULL);
    HIPK_CHECK(hipGetLastError());
    return 0;
 }
