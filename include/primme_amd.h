@@ -386,6 +386,43 @@ int primme_amd_operator_set_amg(struct primme_amd_operator *op, const int32_t *r
 void primme_amd_amg_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME_INT *ldy,
       int *blockSize, struct primme_params *primme, int *ierr);
 void primme_amd_amg_stats(long *applies, long *launches, long *levels);
+/* ---- a hierarchy of the algebraic multigrid preconditioner as an object of its own ----
+ * set_amg[_smoothed] build, upload and tie a hierarchy to one operator in one call; a hierarchy made here is built once and
+ * attached to as many solves and operators over the same matrix as wanted:
+ *    primme_amd_amg_hierarchy_create(op, rowptr_host, colind_host, values_host, smoothed, theta, omega, shift, setup, &h);
+ *    primme_amd_operator_set_amg_hierarchy(op, h, smooth_steps, coarse_steps, over);     then as after set_amg
+ * values_host in the operator's type; smoothed = 0: plain aggregation (omega is not read), 1: smoothed aggregation.
+ * setup = 0: the hierarchy of primme_amd_amg_plan_create[_smoothed] from the host, the very arrays set_amg[_smoothed] upload;
+ * setup = 1 (smoothed only, else -44): the aggregation passes on the host, the prolongator, its transpose, the triple product,
+ * 1 / diag and rho of every level on the device (csrc/hipk_amg_setup.hip), the same hierarchy up to the rounding of the coarse
+ * matrices, whose sums run in another order; a level whose products would pass INT32_MAX entries or the device's memory is
+ * built by the host routines instead (primme_amd_amg_hierarchy_stages counts them; the environment variable
+ * PRIMME_AMD_AMG_SETUP_MAX_ENTRIES, read when a hierarchy is created, lowers that limit).  Any other value of setup returns -1.
+ * The hierarchy owns the device arrays of the levels >= 1, the aggregate maps or P_l / R_l, 1 / diag and the dense inverse of
+ * the last level; level 0 runs on the operator it is attached to.  smooth_steps, coarse_steps and over belong to the
+ * attachment: one hierarchy serves V(1,1) and V(2,2); over must be 1 with a smoothed hierarchy.  Reference-counted: an
+ * operator holds a reference while the hierarchy is attached, either side may be destroyed first, attaching another hierarchy
+ * or calling set_amg* releases the one attached.  It may be attached to several operators over the same matrix, a double and a
+ * float one included (the hierarchy's data is double for both).  Not thread-safe.
+ * create / set_amg_hierarchy: -44 as set_amg; -1 for an argument out of range (as set_amg), a plan the host refuses, a device
+ * failure, an operator whose rows or entries differ from the matrix the hierarchy was built from.
+ * _info: levels, and per level (arrays of PRIMME_AMD_AMG_MAXLEVELS) the rows, the entries of M_l and of P_l; the seconds of
+ * the whole create call and of the device stages in it; how often it was attached.  Any pointer may be NULL.
+ * _stages: the levels that fell back to the host and seconds[PRIMME_AMD_AMG_MAXLEVELS][6] of the device set-up per level:
+ * aggregation (host), P, R, triple product, finish, download of M_{l+1}.
+ * _download: a host primme_amd_amg_plan (primme_amd_io.h; release with primme_amd_amg_plan_free) read back from the device
+ * arrays; level 0 carries n, nnz, dinv, rho, the maps and the transfer matrices but no matrix (rowptr, colind, values NULL). */
+struct primme_amd_amg_hierarchy;
+struct primme_amd_amg_plan;
+int primme_amd_amg_hierarchy_create(struct primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smoothed, double theta, double omega, double shift, int setup, struct primme_amd_amg_hierarchy **h);
+void primme_amd_amg_hierarchy_destroy(struct primme_amd_amg_hierarchy *h);
+int primme_amd_operator_set_amg_hierarchy(struct primme_amd_operator *op, struct primme_amd_amg_hierarchy *h, int smooth_steps,
+      int coarse_steps, double over);
+int primme_amd_amg_hierarchy_info(const struct primme_amd_amg_hierarchy *h, int *nlevels, int64_t *rows, int64_t *nnz, int64_t *pnnz,
+      double *setup_seconds, double *device_seconds, long *times_attached);
+int primme_amd_amg_hierarchy_stages(const struct primme_amd_amg_hierarchy *h, int *fallback_levels, double *seconds);
+int primme_amd_amg_hierarchy_download(const struct primme_amd_amg_hierarchy *h, struct primme_amd_amg_plan **plan);
 /* globalSumReal over RCCL: set primme->commInfo = handle from primme_amd_comm_create().
  * When the solver sees this exact function installed it reduces its DEVICE partials
  * with ncclAllReduce before the (single) device->host copy; called directly it also

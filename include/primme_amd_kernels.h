@@ -510,6 +510,33 @@ int hipk_amg_csr_apply(void *hip_stream, hipk_dtype dt, int64_t nrows, int64_t n
 int hipk_amg_dense_apply(void *hip_stream, hipk_dtype dt, int n, const double *G, int nx, const void *X, int64_t ldx, void *Y,
       int64_t ldy);
 
+/* ---- the row-parallel stages of the smoothed-aggregation set-up (csrc/hipk_amg_setup.hip; no reference
+ * counterpart).  CSR matrices in DEVICE arrays, int32 indices, double values, ascending columns in a row, one entry per
+ * position.  A stage runs a symbolic pass, an exclusive scan and a numeric pass on the stream, allocates its results at their
+ * exact size and returns when they are complete; the results are released with hipk_amg_setup_free.  Deterministic: no
+ * floating-point atomics, every sum has one order.
+ *   hipk_amg_build_prolongation  P (n x nc): row i sums m_iq per aggregate agg[col q] in the row's order, p_iJ = [J = agg[i]]
+ *                                - (w dinv_i) s_J with w = omega / rho; the bits of primme_amd_amg_plan_create_smoothed
+ *   hipk_amg_csr_transpose       T = A' (ncols rows) for an nrows x ncols matrix of nnz entries, the values the same bits
+ *   hipk_amg_galerkin            C = R (M P), nc x nc: B = M P, the upper triangle of R B, mirrored: exactly symmetric.  The
+ *                                sums run in another order than the host's triple loop
+ *   hipk_amg_level_finish        dinv[i] = 1 / m_ii, diag[i] = m_ii (diag may be NULL), *rho = max_i sum_j |m_ij| / m_ii, *flag =
+ *                                1 when a row has no diagonal entry or m_ii <= 0 (rho then covers the other rows)
+ * max_entries: the most entries any array of the stage may have; negative or beyond INT32_MAX reads as INT32_MAX.
+ * Return 0; 1 when a count passes max_entries or the device has no memory: nothing is kept and the caller builds the level on
+ * the host; -1 argument or device error.  Sizes and pointers are checked, the indices TRUSTED. */
+int hipk_amg_build_prolongation(void *hip_stream, int64_t n, int64_t nc, const int32_t *rowptr, const int32_t *colind, const double *values,
+      const double *dinv, const int32_t *agg, double w, int64_t max_entries, int32_t **prowptr, int32_t **pcolind, double **pvalues,
+      int64_t *pnnz);
+int hipk_amg_csr_transpose(void *hip_stream, int64_t nrows, int64_t ncols, int64_t nnz, const int32_t *rowptr, const int32_t *colind,
+      const double *values, int64_t max_entries, int32_t **trowptr, int32_t **tcolind, double **tvalues);
+int hipk_amg_galerkin(void *hip_stream, int64_t n, int64_t nc, const int32_t *rowptr, const int32_t *colind, const double *values,
+      const int32_t *prowptr, const int32_t *pcolind, const double *pvalues, const int32_t *rrowptr, const int32_t *rcolind,
+      const double *rvalues, int64_t max_entries, int32_t **crowptr, int32_t **ccolind, double **cvalues, int64_t *cnnz);
+int hipk_amg_level_finish(void *hip_stream, int64_t n, const int32_t *rowptr, const int32_t *colind, const double *values, double *dinv,
+      double *diag, double *rho, int *flag);
+void hipk_amg_setup_free(void *device_array);
+
 /* ---- Rayleigh-Ritz small solve on the device (reference solve_projection.c:188-331 calls xHEEVX,
  * blaslapack.c:1024-1143).  Symmetric n x n (n <= 64), upper triangle of A_host referenced;
  * eigenvalues ascending in evals_host, orthonormal eigenvectors in Z_host.  One workgroup, parallel

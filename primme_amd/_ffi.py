@@ -361,6 +361,29 @@ def declare_amg(lib):
     lib.hipk_amg_csr_apply.restype = C.c_int
     lib.hipk_amg_dense_apply.argtypes = [_vp, _i, _i, _vp, _i, _vp, _i64, _vp, _i64]
     lib.hipk_amg_dense_apply.restype = C.c_int
+    # the hierarchy as an object of its own and the device stages of its set-up (csrc/hipk_amg_setup.hip)
+    lib.primme_amd_amg_hierarchy_create.argtypes = [_vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _i, P(_vp)]
+    lib.primme_amd_amg_hierarchy_create.restype = C.c_int
+    lib.primme_amd_amg_hierarchy_destroy.argtypes = [_vp]
+    lib.primme_amd_amg_hierarchy_destroy.restype = None
+    lib.primme_amd_operator_set_amg_hierarchy.argtypes = [_vp, _vp, _i, _i, C.c_double]
+    lib.primme_amd_operator_set_amg_hierarchy.restype = C.c_int
+    lib.primme_amd_amg_hierarchy_info.argtypes = [_vp, P(_i), P(_i64), P(_i64), P(_i64), P(C.c_double), P(C.c_double), P(C.c_long)]
+    lib.primme_amd_amg_hierarchy_info.restype = C.c_int
+    lib.primme_amd_amg_hierarchy_stages.argtypes = [_vp, P(_i), P(C.c_double)]
+    lib.primme_amd_amg_hierarchy_stages.restype = C.c_int
+    lib.primme_amd_amg_hierarchy_download.argtypes = [_vp, P(_vp)]
+    lib.primme_amd_amg_hierarchy_download.restype = C.c_int
+    lib.hipk_amg_build_prolongation.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_double, _i64, P(_vp), P(_vp), P(_vp), P(_i64)]
+    lib.hipk_amg_build_prolongation.restype = C.c_int
+    lib.hipk_amg_csr_transpose.argtypes = [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, P(_vp), P(_vp), P(_vp)]
+    lib.hipk_amg_csr_transpose.restype = C.c_int
+    lib.hipk_amg_galerkin.argtypes = [_vp, _i64, _i64] + [_vp] * 9 + [_i64, P(_vp), P(_vp), P(_vp), P(_i64)]
+    lib.hipk_amg_galerkin.restype = C.c_int
+    lib.hipk_amg_level_finish.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _vp, P(C.c_double), P(_i)]
+    lib.hipk_amg_level_finish.restype = C.c_int
+    lib.hipk_amg_setup_free.argtypes = [_vp]
+    lib.hipk_amg_setup_free.restype = None
 
 
 def declare_formats(lib):

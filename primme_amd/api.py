@@ -243,6 +243,33 @@ class Session:
             if op.csr is None:
                 raise ValueError(f"precond={precond!r}: the algebraic multigrid preconditioner reads the CSR arrays of the operator; "
                                  "a stencil operator has precond=('multigrid', dims)")
+        amgh = isinstance(precond, (tuple, list)) and len(precond) > 0 and precond[0] == "amg_hierarchy"
+        if amgh:
+            # every argument error before any library call
+            if not 2 <= len(precond) <= 5:
+                raise ValueError("precond: ('amg_hierarchy', H[, smooth_steps[, coarse_steps[, over]]])")
+            H = precond[1]
+            if not isinstance(H, AmgHierarchy):
+                raise ValueError(f"precond={precond!r}: the second entry is an AmgHierarchy")
+            if H.closed:
+                raise ValueError("precond=('amg_hierarchy', H): H is closed")
+            h_nu = int(precond[2]) if len(precond) > 2 else 2
+            h_ncs = int(precond[3]) if len(precond) > 3 else 16
+            h_over = float(precond[4]) if len(precond) > 4 else 1.0
+            if h_nu < 1 or h_ncs < 1 or not 1.0 <= h_over < 2.0:
+                raise ValueError("precond=('amg_hierarchy', ...): needs steps >= 1 and 1 <= over < 2")
+            if H.smoothed and h_over != 1.0:
+                raise ValueError("precond=('amg_hierarchy', ...): over must be 1 with a smoothed hierarchy")
+            if user_precond is not None:
+                raise ValueError("precond=('amg_hierarchy', ...) and user_precond exclude each other")
+            if self.cplx or self.comm is not None or op.csr is None:
+                raise ValueError("precond=('amg_hierarchy', ...): the algebraic multigrid preconditioner serves real single-rank CSR operators")
+            if (op.nrows, int(op.csr[0][-1])) != (H.n, H.matrix_nnz):
+                raise ValueError(f"precond=('amg_hierarchy', H): H was built from a matrix of {H.n} rows and {H.matrix_nnz} entries, "
+                                 f"the operator has {op.nrows} and {int(op.csr[0][-1])}")
+            if not (self.be.native_operator and hasattr(lib, "primme_amd_operator_set_amg_hierarchy")):
+                raise ValueError(f"precond=('amg_hierarchy', ...): the algebraic multigrid preconditioner runs on the device operator of "
+                                 f"the product library; back end {self.backend!r} has no such operator")
         p = F.PrimmeParams()
         nLocal = op.nrows
         v0 = None if v0 is None else np.asarray(v0, dtype=dtype).reshape(nLocal, -1)
@@ -357,6 +384,16 @@ class Session:
                 p.preconditioner = self.oph
                 p.applyPreconditioner = C.cast(lib.primme_amd_amg_precond, C.c_void_p)
                 p.correctionParams.precondition = 1
+            elif amgh:
+                # ("amg_hierarchy", H[, smooth_steps[, coarse_steps[, over]]]): the cycle of ("amg") / ("amg_smoothed") on a
+                # hierarchy built once (AmgHierarchy); the smoother's parameters belong to this solve
+                rc = lib.primme_amd_operator_set_amg_hierarchy(self.oph, H._handle(self), h_nu, h_ncs, h_over)
+                if rc:
+                    raise ValueError(f"precond=('amg_hierarchy', ...): the hierarchy does not fit this operator ({rc})")
+                lib.primme_amd_amg_stats(None, None, None)              # the counters are per process: start this solve at zero
+                p.preconditioner = self.oph
+                p.applyPreconditioner = C.cast(lib.primme_amd_amg_precond, C.c_void_p)
+                p.correctionParams.precondition = 1
             elif precond is not None:
                 # "jacobi": per-vector shifts of the solver; ("jacobi", s): fixed K = diag(A) - s
                 if precond == "jacobi": lib.primme_amd_operator_set_jacobi(self.oph, 0, 0.0)
@@ -433,11 +470,158 @@ class Session:
             st = [C.c_long(0), C.c_long(0)]
             lib.primme_amd_multigrid_stats(*[C.byref(v) for v in st])
             res.precond_stats = dict(zip(("applies", "launches"), (v.value for v in st)))
-        if amg:
+        if amg or amgh:
             st = [C.c_long(0), C.c_long(0), C.c_long(0)]
             lib.primme_amd_amg_stats(*[C.byref(v) for v in st])
             res.precond_stats = dict(zip(("applies", "launches", "levels"), (v.value for v in st)))
         return res
+
+
+_AMG_MAXLEVELS = 24
+
+
+class _AmgLevel(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("nc", C.c_int64), ("rowptr", C.POINTER(C.c_int32)),
+                ("colind", C.POINTER(C.c_int32)), ("values", C.POINTER(C.c_double)), ("dinv", C.POINTER(C.c_double)),
+                ("rho", C.c_double), ("agg", C.POINTER(C.c_int32)), ("aggptr", C.POINTER(C.c_int32)),
+                ("aggrows", C.POINTER(C.c_int32))]
+
+
+class _AmgTransfer(C.Structure):
+    _fields_ = [("pnnz", C.c_int64), ("prowptr", C.POINTER(C.c_int32)), ("pcolind", C.POINTER(C.c_int32)),
+                ("pvalues", C.POINTER(C.c_double)), ("rrowptr", C.POINTER(C.c_int32)), ("rcolind", C.POINTER(C.c_int32)),
+                ("rvalues", C.POINTER(C.c_double))]
+
+
+class _AmgPlan(C.Structure):
+    """primme_amd_amg_plan of include/primme_amd_io.h"""
+    _fields_ = [("nlevels", C.c_int), ("shift", C.c_double), ("theta", C.c_double), ("level", _AmgLevel * _AMG_MAXLEVELS),
+                ("omega", C.c_double), ("transfer", _AmgTransfer * _AMG_MAXLEVELS)]
+
+
+def amg_download_plan(lib, handle):
+    """primme_amd_amg_hierarchy_download for a hierarchy handle of the C ABI, as AmgHierarchy.plan() returns it"""
+    P = C.POINTER(_AmgPlan)()
+    download = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.POINTER(_AmgPlan)))(("primme_amd_amg_hierarchy_download", lib))
+    free = C.CFUNCTYPE(None, C.POINTER(_AmgPlan))(("primme_amd_amg_plan_free", lib))
+    rc = download(handle, C.byref(P))
+    if rc:
+        raise RuntimeError(f"primme_amd_amg_hierarchy_download failed: {rc}")
+
+    def cp(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(max(int(n), 1),))[:int(n)].astype(dt, copy=True)
+
+    out = []
+    for l in range(P.contents.nlevels):
+        L, X = P.contents.level[l], P.contents.transfer[l]
+        d = dict(n=int(L.n), nnz=int(L.nnz), nc=int(L.nc), rho=float(L.rho), dinv=cp(L.dinv, L.n, np.float64))
+        if L.rowptr:
+            d.update(rowptr=cp(L.rowptr, L.n + 1, np.int64), colind=cp(L.colind, L.nnz, np.int64), values=cp(L.values, L.nnz, np.float64))
+        if L.nc > 0:
+            d.update(agg=cp(L.agg, L.n, np.int64), aggptr=cp(L.aggptr, L.nc + 1, np.int64), aggrows=cp(L.aggrows, L.n, np.int64))
+        if X.prowptr:
+            d.update(pnnz=int(X.pnnz), prowptr=cp(X.prowptr, L.n + 1, np.int64), pcolind=cp(X.pcolind, X.pnnz, np.int64),
+                     pvalues=cp(X.pvalues, X.pnnz, np.float64), rrowptr=cp(X.rrowptr, L.nc + 1, np.int64),
+                     rcolind=cp(X.rcolind, X.pnnz, np.int64), rvalues=cp(X.rvalues, X.pnnz, np.float64))
+        out.append(d)
+    free(P)
+    return out
+
+
+class AmgHierarchy:
+    """The hierarchy of the algebraic multigrid preconditioner as an object: built once, used by any number of solves through
+    precond=("amg_hierarchy", H[, smooth_steps[, coarse_steps[, over]]]), on the Session it was built with or on another Session
+    over the same matrix (a float32 one beside a float64 one, say).
+
+    source: a Session (the hierarchy is built at once) or an Operator (it is built by the first solve that uses it).
+    smoothed=True: smoothed aggregation with the damping omega (over must then be 1 in the solves); False: plain aggregation.
+    setup="device": the prolongator, its transpose, the triple product, 1 / diag and the spectral bounds of every level are
+    built on the device, the aggregation passes on the host (smoothed only); "host": everything on the host, the hierarchy of
+    ("amg_smoothed") / ("amg") bit for bit.  close() releases the handle; a Session it is attached to keeps the device data
+    alive until that Session is closed or given another preconditioner."""
+
+    def __init__(self, source, smoothed=True, theta=0.08, omega=4.0 / 3.0, shift=0.0, setup="device"):
+        if setup not in ("host", "device"):
+            raise ValueError(f"setup={setup!r}: 'host' or 'device'")
+        if setup == "device" and not smoothed:
+            raise ValueError("setup='device' builds the smoothed hierarchy; plain aggregation has setup='host'")
+        if not 0.0 <= theta < 1.0 or not shift >= 0.0 or (smoothed and not 0.0 < omega < 2.0):
+            raise ValueError("needs 0 <= theta < 1, shift >= 0 and 0 < omega < 2")
+        op = source.op if isinstance(source, Session) else source
+        if not isinstance(op, Operator) or op.csr is None:
+            raise ValueError("an AmgHierarchy is built from a Session or an Operator with CSR arrays")
+        self.smoothed, self.theta, self.omega, self.shift, self.setup = bool(smoothed), float(theta), float(omega), float(shift), setup
+        self.n, self.matrix_nnz = int(op.nrows), int(op.csr[0][-1])
+        self.closed = False
+        self._h, self._lib = None, None
+        if isinstance(source, Session):
+            self._handle(source)
+
+    def _handle(self, session):
+        """the library's handle, built with `session`'s operator when there is none yet"""
+        if self.closed:
+            raise ValueError("the AmgHierarchy is closed")
+        if self._h is None:
+            lib, op = session.lib, session.op
+            if not (session.be.native_operator and hasattr(lib, "primme_amd_amg_hierarchy_create")):
+                raise ValueError(f"an AmgHierarchy lives on the device of the product library; back end {session.backend!r} has none")
+            if session.cplx or session.comm is not None or op.csr is None or (op.nrows, int(op.csr[0][-1])) != (self.n, self.matrix_nnz):
+                raise ValueError("an AmgHierarchy is built with a real single-rank CSR operator, the one it was made for")
+            rp = np.ascontiguousarray(op.csr[0], dtype=np.int32)
+            ci = np.ascontiguousarray(op.csr[1], dtype=np.int32)
+            va = np.ascontiguousarray(op.csr[2], dtype=session.dtype)
+            h = C.c_void_p()
+            rc = lib.primme_amd_amg_hierarchy_create(session.oph, rp.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                                     va.ctypes.data_as(C.c_void_p), int(self.smoothed), self.theta, self.omega, self.shift,
+                                                     1 if self.setup == "device" else 0, C.byref(h))
+            if rc:
+                raise ValueError(f"AmgHierarchy: the library refuses the matrix or the parameters ({rc}): it needs a symmetric matrix "
+                                 "with a positive diagonal on every level")
+            self._h, self._lib = h, lib
+        return self._h
+
+    def _info(self):
+        if self._h is None:
+            raise ValueError("the AmgHierarchy is closed" if self.closed else "the AmgHierarchy is not built yet: its first solve builds it")
+        nl, att = C.c_int(0), C.c_long(0)
+        rows, nnz, pnnz = ((C.c_int64 * _AMG_MAXLEVELS)() for _ in range(3))
+        ss, ds = C.c_double(0), C.c_double(0)
+        self._lib.primme_amd_amg_hierarchy_info(self._h, C.byref(nl), rows, nnz, pnnz, C.byref(ss), C.byref(ds), C.byref(att))
+        fb = C.c_int(0)
+        stages = (C.c_double * (_AMG_MAXLEVELS * 6))()
+        self._lib.primme_amd_amg_hierarchy_stages(self._h, C.byref(fb), stages)
+        k = nl.value
+        return dict(levels=k, rows=list(rows[:k]), nnz=list(nnz[:k]), pnnz=list(pnnz[:k]), setup_seconds=ss.value, device_seconds=ds.value,
+                    times_attached=att.value, fallback_levels=fb.value,
+                    stage_seconds=[dict(zip(("aggregate", "prolongation", "transpose", "galerkin", "finish", "download"), stages[6 * l:6 * l + 6]))
+                                   for l in range(max(k - 1, 0))])
+
+    levels = property(lambda self: self._info()["levels"])
+    rows = property(lambda self: self._info()["rows"])
+    nnz = property(lambda self: self._info()["nnz"])
+    setup_seconds = property(lambda self: self._info()["setup_seconds"])
+    device_seconds = property(lambda self: self._info()["device_seconds"])
+    fallback_levels = property(lambda self: self._info()["fallback_levels"])
+    times_attached = property(lambda self: self._info()["times_attached"])
+    stage_seconds = property(lambda self: self._info()["stage_seconds"])
+
+    def plan(self):
+        """the hierarchy read back from the device: a list of dicts per level (n, nnz, nc, rho, dinv; from level 1 on rowptr,
+        colind, values; but on the last level agg, aggptr, aggrows and, smoothed, pnnz, prowptr, pcolind, pvalues, rrowptr,
+        rcolind, rvalues) as numpy arrays.  Level 0 has no matrix: it is the operator's."""
+        self._info()
+        return amg_download_plan(self._lib, self._h)
+
+    def close(self):
+        if self._h is not None:
+            self._lib.primme_amd_amg_hierarchy_destroy(self._h)
+        self._h, self.closed = None, True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def eigsh(op, backend="hip", comm=None, dtype=np.float64, complex_form="native", mass=None, **kw):

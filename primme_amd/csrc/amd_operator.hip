@@ -9,6 +9,8 @@
 #include "comm_internal.h"
 #include "eigs_internal.h"   /* primme_amd_svds_operator_is_local */
 #include "primme_amd_io.h"     /* primme_amd_amg_plan */
+#include "amg_internal.h"      /* the host stages of the hierarchy's device set-up */
+#include <time.h>
 
 /* aggregation AMG preconditioner (primme_amd_amg_precond): the hierarchy on the device, nlev = 0 until configured.  Level l
    has n rows, nc aggregates (0 on the last level), the operator M (level 0: NULL, the operator's own matrix serves with the
@@ -16,21 +18,42 @@
    column (16-byte columns).  G: the dense inverse of the last level when it has at most PRIMME_AMD_AMG_DENSE_ROWS rows.
    buf: ONE allocation of cols columns per panel, level 0 an iterate and the product, every other level the right-hand side,
    two iterates and the product.  Smoothed aggregation (set_amg_smoothed): P_l (n rows) and R_l = P_l' (nc rows) in CSR with
-   double values, NULL for plain aggregation */
+   double values, NULL for plain aggregation.
+   The levels live in a reference-counted HIERARCHY (primme_amd_amg_hierarchy_create) that several operators over
+   the same matrix may share: the handle its creator holds counts one, every operator it is attached to one.  Beside the
+   operator M[0] (double panels) / M[1] (float panels) of a level >= 1, made when the hierarchy is first attached to an operator
+   of that type, it keeps the level's CSR arrays in double (mrp, mci, mva): what the device set-up builds, what the operators are
+   made from and what primme_amd_amg_hierarchy_download reads.  An operator's own state is the attachment: the smoother's
+   parameters, the operator type and the scratch panels */
 struct amg_level_dev {
-   int64_t n, nc, ld;
+   int64_t n, nc, ld, nnz, pnnz;
    double rho;
-   hipk_csr *M;
+   hipk_csr *M[2];
+   int32_t *mrp, *mci;
+   double *mva;
    double *dinv;
    int32_t *agg, *aggptr, *aggrows;
    int32_t *prp, *pci, *rrp, *rci;
    double *pva, *rva;
 };
-struct amg_state {
-   int nlev, nu, cs, cols;
-   double over, shift;
+#define AMG_NSTAGES 6                       /* aggregation (host), P, R, triple product, finish, download of M_{l+1} */
+struct primme_amd_amg_hierarchy {
+   int refs, nlev, smoothed, fallback, own_ctx;
+   int priv;                                /* 1 + the operator type (0 double, 1 float) of the one operator a private hierarchy of
+                                               set_amg[_smoothed] serves: its level operators are made at once, no CSR arrays kept */
+   int64_t max_entries;                     /* the entry limit of the device stages */
+   long attached;
+   hipk_ctx *ctx;
+   double shift, theta, omega;
+   int64_t n0, nnz0;
    amg_level_dev lv[PRIMME_AMD_AMG_MAXLEVELS];
    double *G;
+   double setup_seconds, device_seconds, stage[PRIMME_AMD_AMG_MAXLEVELS][AMG_NSTAGES];
+};
+struct amg_state {
+   primme_amd_amg_hierarchy *h;             /* NULL until configured */
+   int dti, nu, cs, cols;
+   double over;
    void *buf;
 };
 
@@ -598,29 +621,324 @@ extern "C" void primme_amd_amg_stats(long *applies, long *launches, long *levels
    g_amg_applies = g_amg_launches = g_amg_levels = 0;
 }
 
+static double amg_now(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+static void amg_free_dev(void *pp) {
+   void **p = (void **)pp;
+   if (*p) (void)hipFree(*p);
+   *p = NULL;
+}
+/* the CSR arrays of a level's matrix and, with all = 1, everything else the level holds */
+static void amg_level_release(amg_level_dev *L, int all) {
+   amg_free_dev(&L->mrp); amg_free_dev(&L->mci); amg_free_dev(&L->mva);
+   if (!all) return;
+   for (int k = 0; k < 2; k++)
+      if (L->M[k]) { (void)hipk_csr_destroy(L->M[k]); L->M[k] = NULL; }
+   amg_free_dev(&L->dinv); amg_free_dev(&L->agg); amg_free_dev(&L->aggptr); amg_free_dev(&L->aggrows);
+   amg_free_dev(&L->prp); amg_free_dev(&L->pci); amg_free_dev(&L->pva); amg_free_dev(&L->rrp); amg_free_dev(&L->rci); amg_free_dev(&L->rva);
+}
+static void amg_hierarchy_unref(primme_amd_amg_hierarchy *h) {
+   if (!h || --h->refs > 0) return;
+   for (int l = 0; l < PRIMME_AMD_AMG_MAXLEVELS; l++) amg_level_release(&h->lv[l], 1);
+   amg_free_dev(&h->G);
+   if (h->own_ctx && h->ctx) (void)hipk_ctx_destroy(h->ctx);
+   free(h);
+}
 static void amg_release(amg_state *s) {
-   for (int l = 0; l < PRIMME_AMD_AMG_MAXLEVELS; l++) {
-      amg_level_dev *L = &s->lv[l];
-      if (L->M) (void)hipk_csr_destroy(L->M);
-      if (L->dinv) (void)hipFree(L->dinv);
-      if (L->agg) (void)hipFree(L->agg);
-      if (L->aggptr) (void)hipFree(L->aggptr);
-      if (L->aggrows) (void)hipFree(L->aggrows);
-      if (L->prp) (void)hipFree(L->prp);
-      if (L->pci) (void)hipFree(L->pci);
-      if (L->pva) (void)hipFree(L->pva);
-      if (L->rrp) (void)hipFree(L->rrp);
-      if (L->rci) (void)hipFree(L->rci);
-      if (L->rva) (void)hipFree(L->rva);
-   }
-   if (s->G) (void)hipFree(s->G);
    if (s->buf) (void)hipFree(s->buf);
+   amg_hierarchy_unref(s->h);
    memset(s, 0, sizeof(*s));
 }
 /* a device copy of `bytes` host bytes; 0 on success */
 static int amg_to_device(hipk_ctx *ctx, void **dst, const void *src, size_t bytes) {
    if (hipMalloc(dst, bytes ? bytes : 1) != hipSuccess) { *dst = NULL; return -2; }
    return bytes ? hipk_upload(ctx, *dst, src, bytes) : 0;
+}
+/* a host copy of `count` elements of a device array; NULL: no memory or the copy failed */
+template <typename T> static T *amg_to_host(hipk_ctx *ctx, const T *src, int64_t count) {
+   T *dst = (T *)malloc(sizeof(T) * (size_t)(count > 0 ? count : 1));
+   if (dst && count > 0 && hipk_download(ctx, dst, src, sizeof(T) * (size_t)count)) { free(dst); dst = NULL; }
+   return dst;
+}
+
+/* the operator of a level for panels of type dti (0 double, 1 float) from the level's host CSR arrays in double */
+static int amg_level_operator(hipk_ctx *ctx, int dti, int64_t n, int64_t nnz, const int32_t *rp, const int32_t *ci, const double *va, hipk_csr **M) {
+   if (dti == 0) return hipk_csr_create(ctx, HIPK_F64, n, n, 0, rp, ci, va, M);
+   float *vf = (float *)malloc(sizeof(float) * (size_t)(nnz > 0 ? nnz : 1));
+   if (!vf) return -2;
+   for (int64_t q = 0; q < nnz; q++) vf[q] = (float)va[q];
+   const int rc = hipk_csr_create(ctx, HIPK_F32, n, n, 0, rp, ci, vf, M);
+   free(vf);
+   return rc;
+}
+
+/* level l of the host plan P on the device: dinv, the matrix (l >= 1), the aggregate maps and the transfer matrices */
+static int amg_upload_level(primme_amd_amg_hierarchy *h, int l, const primme_amd_amg_plan *P) {
+   const primme_amd_amg_level *H = &P->level[l];
+   const primme_amd_amg_transfer *X = &P->transfer[l];
+   amg_level_dev *L = &h->lv[l];
+   hipk_ctx *ctx = h->ctx;
+   L->n = H->n; L->nc = H->nc; L->nnz = H->nnz; L->rho = H->rho; L->ld = (H->n + 3) / 4 * 4; L->pnnz = 0;
+   int rc = L->dinv ? 0 : amg_to_device(ctx, (void **)&L->dinv, H->dinv, sizeof(double) * (size_t)H->n);
+   if (!rc && l > 0 && h->priv) {
+      if (!L->M[h->priv - 1]) rc = amg_level_operator(ctx, h->priv - 1, H->n, H->nnz, H->rowptr, H->colind, H->values, &L->M[h->priv - 1]);
+   } else if (!rc && l > 0 && !L->mrp) {
+      rc = amg_to_device(ctx, (void **)&L->mrp, H->rowptr, sizeof(int32_t) * (size_t)(H->n + 1));
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->mci, H->colind, sizeof(int32_t) * (size_t)H->nnz);
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->mva, H->values, sizeof(double) * (size_t)H->nnz);
+   }
+   if (!rc && H->nc > 0 && !L->agg) {
+      rc = amg_to_device(ctx, (void **)&L->agg, H->agg, sizeof(int32_t) * (size_t)H->n);
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->aggptr, H->aggptr, sizeof(int32_t) * (size_t)(H->nc + 1));
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->aggrows, H->aggrows, sizeof(int32_t) * (size_t)H->n);
+   }
+   if (!rc && H->nc > 0 && X->prowptr) {
+      L->pnnz = X->pnnz;
+      rc = amg_to_device(ctx, (void **)&L->prp, X->prowptr, sizeof(int32_t) * (size_t)(H->n + 1));
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->pci, X->pcolind, sizeof(int32_t) * (size_t)X->pnnz);
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->pva, X->pvalues, sizeof(double) * (size_t)X->pnnz);
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->rrp, X->rrowptr, sizeof(int32_t) * (size_t)(H->nc + 1));
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->rci, X->rcolind, sizeof(int32_t) * (size_t)X->pnnz);
+      if (!rc) rc = amg_to_device(ctx, (void **)&L->rva, X->rvalues, sizeof(double) * (size_t)X->pnnz);
+   }
+   return rc;
+}
+
+/* the operators of the levels >= 1 for panels of type dti (0 double, 1 float), from the levels' CSR arrays */
+static int amg_level_operators(primme_amd_amg_hierarchy *h, int dti) {
+   int rc = 0;
+   for (int l = 1; l < h->nlev && !rc; l++) {
+      amg_level_dev *L = &h->lv[l];
+      if (L->M[dti]) continue;
+      if (!L->mrp) return -1;                      /* a private hierarchy serves the operator type it was made for */
+      int32_t *rp = amg_to_host(h->ctx, L->mrp, L->n + 1), *ci = amg_to_host(h->ctx, L->mci, L->nnz);
+      double *va = amg_to_host(h->ctx, L->mva, L->nnz);
+      rc = (rp && ci && va) ? amg_level_operator(h->ctx, dti, L->n, L->nnz, rp, ci, va, &L->M[dti]) : -2;
+      free(rp); free(ci); free(va);
+   }
+   return rc;
+}
+
+/* The smoothed set-up with its row-parallel stages on the device (hipk_amg_setup.hip).  Per level: the host
+ * aggregates M_l (pa_amg_level_aggregate: the passes of 4o, untouched), the maps are uploaded, the device builds P_l, R_l,
+ * M_{l+1}, dinv_{l+1} and rho_{l+1}, and M_{l+1} with its diagonal comes back for the next aggregation and stays resident.
+ * A stage that answers 1 (a count beyond the entry limit, no device memory) sends the LEVEL to the host routines
+ * (pa_amg_prolongation, pa_amg_galerkin_general), whose results are uploaded, and the build goes on.  P keeps the host side of
+ * the build: the level matrices always, transfer matrices only where a level fell back. */
+static int amg_build_device(primme_amd_amg_hierarchy *h, primme_amd_amg_plan *P, int64_t n, const int32_t *rowptr, const int32_t *colind,
+      const void *values, size_t elem_size) {
+   double *dg = (double *)malloc(sizeof(double) * (size_t)n);
+   int32_t *tmp = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
+   void *st = hipk_ctx_stream(h->ctx);
+   int rc = (dg && tmp) ? 0 : -5;
+   if (!rc) rc = pa_amg_level0(n, rowptr, colind, values, elem_size, h->shift, &P->level[0], dg);
+   if (!rc) {                                      /* level 0 in double beside the operator's own copy, until level 1 stands */
+      const primme_amd_amg_level *H = &P->level[0];
+      amg_level_dev *L = &h->lv[0];
+      rc = amg_to_device(h->ctx, (void **)&L->mrp, H->rowptr, sizeof(int32_t) * (size_t)(n + 1));
+      if (!rc) rc = amg_to_device(h->ctx, (void **)&L->mci, H->colind, sizeof(int32_t) * (size_t)H->nnz);
+      if (!rc) rc = amg_to_device(h->ctx, (void **)&L->mva, H->values, sizeof(double) * (size_t)H->nnz);
+   }
+   int l = 0;
+   while (!rc) {
+      primme_amd_amg_level *H = &P->level[l], *Hn = &P->level[l + 1];
+      amg_level_dev *L = &h->lv[l], *N = &h->lv[l + 1];
+      if (H->n <= PRIMME_AMD_AMG_DENSE_ROWS || l + 1 >= PRIMME_AMD_AMG_MAXLEVELS) break;
+      double t = amg_now();
+      rc = pa_amg_level_aggregate(H, dg, h->theta, tmp);
+      h->stage[l][0] = amg_now() - t;
+      if (rc) { rc = rc > 0 ? 0 : rc; break; }     /* 1: stalled, this level is the last */
+      rc = amg_upload_level(h, l, P);              /* dinv (level 0) and the aggregate maps */
+      if (rc) break;
+      const int64_t nc = H->nc;
+      int64_t pnnz = 0, cnnz = 0;
+      double *diag = NULL, rho = 0.0;
+      int flag = 0;
+      const double t0 = amg_now();
+      int drc = hipk_amg_build_prolongation(st, H->n, nc, L->mrp, L->mci, L->mva, L->dinv, L->agg, h->omega / H->rho, h->max_entries, &L->prp, &L->pci, &L->pva, &pnnz);
+      const double t1 = amg_now();
+      if (!drc) drc = hipk_amg_csr_transpose(st, H->n, nc, pnnz, L->prp, L->pci, L->pva, h->max_entries, &L->rrp, &L->rci, &L->rva);
+      const double t2 = amg_now();
+      if (!drc) drc = hipk_amg_galerkin(st, H->n, nc, L->mrp, L->mci, L->mva, L->prp, L->pci, L->pva, L->rrp, L->rci, L->rva, h->max_entries, &N->mrp, &N->mci, &N->mva, &cnnz);
+      const double t3 = amg_now();
+      if (!drc && (hipMalloc((void **)&N->dinv, sizeof(double) * (size_t)nc) != hipSuccess || hipMalloc((void **)&diag, sizeof(double) * (size_t)nc) != hipSuccess)) {
+         (void)hipGetLastError();
+         drc = 1;
+      }
+      if (!drc) drc = hipk_amg_level_finish(st, nc, N->mrp, N->mci, N->mva, N->dinv, diag, &rho, &flag);
+      const double t4 = amg_now();
+      if (!drc && flag) rc = -1;                   /* a row of M_{l+1} without a diagonal entry, or m_ii <= 0 */
+      if (!drc && !rc) {
+         L->pnnz = pnnz;
+         Hn->n = nc; Hn->nnz = cnnz; Hn->rho = rho;
+         Hn->rowptr = amg_to_host(h->ctx, N->mrp, nc + 1);
+         Hn->colind = amg_to_host(h->ctx, N->mci, cnnz);
+         Hn->values = amg_to_host(h->ctx, N->mva, cnnz);
+         Hn->dinv = amg_to_host(h->ctx, N->dinv, nc);
+         if (!Hn->rowptr || !Hn->colind || !Hn->values || !Hn->dinv || hipk_download(h->ctx, dg, diag, sizeof(double) * (size_t)nc)) rc = -5;
+         N->n = nc; N->nnz = cnnz; N->rho = rho; N->ld = (nc + 3) / 4 * 4;
+         h->stage[l][1] = t1 - t0; h->stage[l][2] = t2 - t1; h->stage[l][3] = t3 - t2; h->stage[l][4] = t4 - t3; h->stage[l][5] = amg_now() - t4;
+         h->device_seconds += t4 - t0;
+      }
+      amg_free_dev(&diag);
+      if (drc < 0) rc = -1;
+      if (drc == 1) {                              /* the level on the host, nothing of the device's attempt kept */
+         amg_free_dev(&L->prp); amg_free_dev(&L->pci); amg_free_dev(&L->pva); amg_free_dev(&L->rrp); amg_free_dev(&L->rci); amg_free_dev(&L->rva);
+         amg_level_release(N, 1);
+         /* the same lines of the stage table: P with its transpose, the triple product, the finish, and the upload in the
+            place of the download */
+         const double h0 = amg_now();
+         rc = pa_amg_prolongation(H, h->omega, &P->transfer[l]);
+         const double h1 = amg_now();
+         if (!rc) rc = pa_amg_galerkin_general(H, &P->transfer[l], Hn);
+         const double h2 = amg_now();
+         if (!rc) rc = pa_amg_level_finish(Hn, dg);
+         const double h3 = amg_now();
+         if (!rc) rc = amg_upload_level(h, l, P);
+         if (!rc) rc = amg_upload_level(h, l + 1, P);
+         h->stage[l][1] = h1 - h0; h->stage[l][2] = 0.0; h->stage[l][3] = h2 - h1; h->stage[l][4] = h3 - h2; h->stage[l][5] = amg_now() - h3;
+         h->fallback++;
+      }
+      if (l == 0) amg_level_release(L, 0);         /* level 0 runs on the operator it is attached to */
+      l++;
+   }
+   if (!rc && h->lv[0].mrp) amg_level_release(&h->lv[0], 0);
+   if (!rc && l == 0) rc = amg_upload_level(h, 0, P);                      /* one level: dinv */
+   free(dg); free(tmp);
+   P->nlevels = l + 1;
+   return rc;
+}
+
+/* priv = 1: the private hierarchy of set_amg[_smoothed]: the host route under the operator's own context, which outlives it,
+   the level operators of the operator's type made straight from the host plan.  Never handed to a caller. */
+static int amg_hierarchy_build(primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smoothed, double theta, double omega, double shift, int setup, int priv, primme_amd_amg_hierarchy **out) {
+   if (out) *out = NULL;
+   if (!op || !out) return -1;
+   const hipk_dtype dt = hipk_csr_dtype(op->A);
+   if (op->mode != 0 || (op->comm && primme_amd_comm_size(op->comm) > 1) || op->ldscale != 1 || (dt != HIPK_F64 && dt != HIPK_F32)) return -44;
+   if (hipk_csr_kind(op->A) != 0 || op->lo > 0 || op->hi > 0) return -44;          /* a stencil has ("multigrid", ...) */
+   if (setup != 0 && setup != 1) return -1;
+   if (setup == 1 && !smoothed) return -44;        /* the plain set-up is the sequential aggregation: the host route only */
+   if (!rowptr_host || !colind_host || !values_host || !(theta >= 0.0 && theta < 1.0) || !(shift >= 0.0)) return -1;
+   if (smoothed && !(omega > 0.0 && omega < 2.0)) return -1;
+   const int64_t n = hipk_csr_nrows(op->A);
+   if (n < 1 || rowptr_host[0] != 0 || (int64_t)rowptr_host[n] != hipk_csr_nnz(op->A)) return -1;
+   const size_t es = dt == HIPK_F64 ? 8 : 4;
+   const double t0 = amg_now();
+   primme_amd_amg_hierarchy *h = (primme_amd_amg_hierarchy *)calloc(1, sizeof(*h));
+   if (!h) return -1;
+   h->refs = 1; h->smoothed = smoothed != 0; h->shift = shift; h->theta = theta; h->omega = smoothed ? omega : 0.0;
+   h->n0 = n; h->nnz0 = rowptr_host[n];
+   h->max_entries = INT32_MAX;
+   if (setup == 1) {
+      /* PRIMME_AMD_AMG_SETUP_MAX_ENTRIES lowers the entry limit beyond which a level is built by the host routines (the
+         tests reach that path with it; read when a hierarchy is created) */
+      const char *e = getenv("PRIMME_AMD_AMG_SETUP_MAX_ENTRIES");
+      if (e && *e) { const long long v = atoll(e); if (v >= 0 && v < INT32_MAX) h->max_entries = v; }
+   }
+   if (priv) { h->ctx = hipk_csr_ctx(op->A); h->priv = 1 + (dt == HIPK_F64 ? 0 : 1); }
+   else if (hipk_ctx_create(&h->ctx, NULL)) { free(h); return -1; }
+   else h->own_ctx = 1;
+   primme_amd_amg_plan *P = NULL;
+   int rc = 0;
+   if (setup == 1) {
+      P = (primme_amd_amg_plan *)calloc(1, sizeof(*P));
+      rc = P ? amg_build_device(h, P, n, rowptr_host, colind_host, values_host, es) : -5;
+   } else {
+      rc = smoothed ? primme_amd_amg_plan_create_smoothed(n, rowptr_host, colind_host, values_host, es, shift, theta, omega, &P)
+                    : primme_amd_amg_plan_create(n, rowptr_host, colind_host, values_host, es, shift, theta, &P);
+      for (int l = 0; !rc && l < P->nlevels; l++) rc = amg_upload_level(h, l, P);
+   }
+   if (!rc) {
+      h->nlev = P->nlevels;
+      const int64_t nl = P->level[P->nlevels - 1].n;
+      if (nl <= PRIMME_AMD_AMG_DENSE_ROWS) {
+         double *G = (double *)malloc(sizeof(double) * (size_t)(nl * nl));
+         rc = G ? primme_amd_amg_coarse_inverse(P, G) : -2;             /* -1: the matrix is not positive definite */
+         if (!rc) rc = amg_to_device(h->ctx, (void **)&h->G, G, sizeof(double) * (size_t)(nl * nl));
+         free(G);
+      }
+   }
+   primme_amd_amg_plan_free(P);
+   if (rc) { amg_hierarchy_unref(h); return -1; }
+   h->setup_seconds = amg_now() - t0;
+   *out = h;
+   return 0;
+}
+
+extern "C" int primme_amd_amg_hierarchy_create(primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
+      const void *values_host, int smoothed, double theta, double omega, double shift, int setup, primme_amd_amg_hierarchy **out) {
+   return amg_hierarchy_build(op, rowptr_host, colind_host, values_host, smoothed, theta, omega, shift, setup, 0, out);
+}
+
+extern "C" void primme_amd_amg_hierarchy_destroy(primme_amd_amg_hierarchy *h) { amg_hierarchy_unref(h); }
+
+extern "C" int primme_amd_operator_set_amg_hierarchy(primme_amd_operator *op, primme_amd_amg_hierarchy *h, int smooth_steps, int coarse_steps,
+      double over) {
+   if (!op || !h) return -1;
+   const hipk_dtype dt = hipk_csr_dtype(op->A);
+   if (op->mode != 0 || (op->comm && primme_amd_comm_size(op->comm) > 1) || op->ldscale != 1 || (dt != HIPK_F64 && dt != HIPK_F32)) return -44;
+   if (hipk_csr_kind(op->A) != 0 || op->lo > 0 || op->hi > 0) return -44;
+   if (smooth_steps < 1 || coarse_steps < 1 || !(over >= 1.0 && over < 2.0) || (h->smoothed && over != 1.0)) return -1;
+   if (hipk_csr_nrows(op->A) != h->n0 || hipk_csr_nnz(op->A) != h->nnz0) return -1;
+   const int dti = dt == HIPK_F64 ? 0 : 1;
+   if (amg_level_operators(h, dti)) return -1;
+   h->refs++;                                       /* before the release: h may be the hierarchy attached now */
+   h->attached++;
+   amg_release(&op->amg);
+   op->amg.h = h; op->amg.dti = dti; op->amg.nu = smooth_steps; op->amg.cs = coarse_steps; op->amg.over = over;
+   return 0;
+}
+
+extern "C" int primme_amd_amg_hierarchy_info(const primme_amd_amg_hierarchy *h, int *nlevels, int64_t *rows, int64_t *nnz, int64_t *pnnz,
+      double *setup_seconds, double *device_seconds, long *times_attached) {
+   if (!h) return -1;
+   if (nlevels) *nlevels = h->nlev;
+   for (int l = 0; l < PRIMME_AMD_AMG_MAXLEVELS; l++) {
+      if (rows) rows[l] = l < h->nlev ? h->lv[l].n : 0;
+      if (nnz) nnz[l] = l < h->nlev ? (l == 0 ? h->nnz0 : h->lv[l].nnz) : 0;
+      if (pnnz) pnnz[l] = l < h->nlev ? h->lv[l].pnnz : 0;
+   }
+   if (setup_seconds) *setup_seconds = h->setup_seconds;
+   if (device_seconds) *device_seconds = h->device_seconds;
+   if (times_attached) *times_attached = h->attached;
+   return 0;
+}
+
+extern "C" int primme_amd_amg_hierarchy_stages(const primme_amd_amg_hierarchy *h, int *fallback_levels, double *seconds) {
+   if (!h) return -1;
+   if (fallback_levels) *fallback_levels = h->fallback;
+   if (seconds) memcpy(seconds, h->stage, sizeof(h->stage));
+   return 0;
+}
+
+extern "C" int primme_amd_amg_hierarchy_download(const primme_amd_amg_hierarchy *h, primme_amd_amg_plan **plan) {
+   if (plan) *plan = NULL;
+   if (!h || !plan) return -1;
+   primme_amd_amg_plan *P = (primme_amd_amg_plan *)calloc(1, sizeof(*P));
+   if (!P) return -5;
+   int ok = 1;
+   P->nlevels = h->nlev; P->shift = h->shift; P->theta = h->theta; P->omega = h->omega;
+   for (int l = 0; l < h->nlev && ok; l++) {
+      const amg_level_dev *L = &h->lv[l];
+      primme_amd_amg_level *H = &P->level[l];
+      primme_amd_amg_transfer *X = &P->transfer[l];
+      H->n = L->n; H->nc = L->nc; H->rho = L->rho; H->nnz = l == 0 ? h->nnz0 : L->nnz;
+      ok = (H->dinv = amg_to_host(h->ctx, L->dinv, L->n)) != NULL;
+      if (ok && l > 0) ok = (H->rowptr = amg_to_host(h->ctx, L->mrp, L->n + 1)) && (H->colind = amg_to_host(h->ctx, L->mci, L->nnz)) &&
+                            (H->values = amg_to_host(h->ctx, L->mva, L->nnz));
+      if (ok && L->nc > 0) ok = (H->agg = amg_to_host(h->ctx, L->agg, L->n)) && (H->aggptr = amg_to_host(h->ctx, L->aggptr, L->nc + 1)) &&
+                                (H->aggrows = amg_to_host(h->ctx, L->aggrows, L->n));
+      if (ok && L->prp) {
+         X->pnnz = L->pnnz;
+         ok = (X->prowptr = amg_to_host(h->ctx, L->prp, L->n + 1)) && (X->pcolind = amg_to_host(h->ctx, L->pci, L->pnnz)) &&
+              (X->pvalues = amg_to_host(h->ctx, L->pva, L->pnnz)) && (X->rrowptr = amg_to_host(h->ctx, L->rrp, L->nc + 1)) &&
+              (X->rcolind = amg_to_host(h->ctx, L->rci, L->pnnz)) && (X->rvalues = amg_to_host(h->ctx, L->rva, L->pnnz));
+      }
+   }
+   if (!ok) { primme_amd_amg_plan_free(P); return -5; }
+   *plan = P;
+   return 0;
 }
 
 /* omega = 0: plain aggregation with the over-correction `over`; omega in (0, 2): smoothed aggregation, over = 1 */
@@ -634,57 +952,13 @@ static int amg_configure(primme_amd_operator *op, const int32_t *rowptr_host, co
        !(over >= 1.0 && over < 2.0) || !(shift >= 0.0)) return -1;
    const int64_t n = hipk_csr_nrows(op->A);
    if (n < 1 || rowptr_host[0] != 0 || (int64_t)rowptr_host[n] != hipk_csr_nnz(op->A)) return -1;
-   primme_amd_amg_plan *P = NULL;
-   if (omega == 0.0 ? primme_amd_amg_plan_create(n, rowptr_host, colind_host, values_host, dt == HIPK_F64 ? 8 : 4, shift, theta, &P)
-                    : primme_amd_amg_plan_create_smoothed(n, rowptr_host, colind_host, values_host, dt == HIPK_F64 ? 8 : 4, shift, theta, omega, &P))
-      return -1;
-   hipk_ctx *ctx = hipk_csr_ctx(op->A);
-   amg_state s;
-   memset(&s, 0, sizeof(s));
-   s.nlev = P->nlevels; s.nu = smooth_steps; s.cs = coarse_steps; s.over = over; s.shift = shift;
-   int rc = 0;
-   for (int l = 0; l < P->nlevels && !rc; l++) {
-      const primme_amd_amg_level *H = &P->level[l];
-      amg_level_dev *L = &s.lv[l];
-      L->n = H->n; L->nc = H->nc; L->rho = H->rho; L->ld = (H->n + 3) / 4 * 4;
-      rc = amg_to_device(ctx, (void **)&L->dinv, H->dinv, sizeof(double) * (size_t)H->n);
-      if (!rc && l > 0) {
-         if (dt == HIPK_F64) rc = hipk_csr_create(ctx, dt, H->n, H->n, 0, H->rowptr, H->colind, H->values, &L->M);
-         else {
-            float *vf = (float *)malloc(sizeof(float) * (size_t)(H->nnz > 0 ? H->nnz : 1));
-            if (!vf) rc = -2;
-            for (int64_t q = 0; q < H->nnz && !rc; q++) vf[q] = (float)H->values[q];
-            if (!rc) rc = hipk_csr_create(ctx, dt, H->n, H->n, 0, H->rowptr, H->colind, vf, &L->M);
-            free(vf);
-         }
-      }
-      if (!rc && H->nc > 0) {
-         rc = amg_to_device(ctx, (void **)&L->agg, H->agg, sizeof(int32_t) * (size_t)H->n);
-         if (!rc) rc = amg_to_device(ctx, (void **)&L->aggptr, H->aggptr, sizeof(int32_t) * (size_t)(H->nc + 1));
-         if (!rc) rc = amg_to_device(ctx, (void **)&L->aggrows, H->aggrows, sizeof(int32_t) * (size_t)H->n);
-      }
-      const primme_amd_amg_transfer *X = &P->transfer[l];
-      if (!rc && H->nc > 0 && X->prowptr) {
-         rc = amg_to_device(ctx, (void **)&L->prp, X->prowptr, sizeof(int32_t) * (size_t)(H->n + 1));
-         if (!rc) rc = amg_to_device(ctx, (void **)&L->pci, X->pcolind, sizeof(int32_t) * (size_t)X->pnnz);
-         if (!rc) rc = amg_to_device(ctx, (void **)&L->pva, X->pvalues, sizeof(double) * (size_t)X->pnnz);
-         if (!rc) rc = amg_to_device(ctx, (void **)&L->rrp, X->rrowptr, sizeof(int32_t) * (size_t)(H->nc + 1));
-         if (!rc) rc = amg_to_device(ctx, (void **)&L->rci, X->rcolind, sizeof(int32_t) * (size_t)X->pnnz);
-         if (!rc) rc = amg_to_device(ctx, (void **)&L->rva, X->rvalues, sizeof(double) * (size_t)X->pnnz);
-      }
-   }
-   const int64_t nl = P->level[P->nlevels - 1].n;
-   if (!rc && nl <= PRIMME_AMD_AMG_DENSE_ROWS) {
-      double *G = (double *)malloc(sizeof(double) * (size_t)(nl * nl));
-      rc = G ? primme_amd_amg_coarse_inverse(P, G) : -2;             /* -1: the matrix is not positive definite */
-      if (!rc) rc = amg_to_device(ctx, (void **)&s.G, G, sizeof(double) * (size_t)(nl * nl));
-      free(G);
-   }
-   primme_amd_amg_plan_free(P);
-   if (rc) { amg_release(&s); return -1; }
-   amg_release(&op->amg);                           /* the operator changes only when everything is in order */
-   op->amg = s;
-   return 0;
+   /* a private hierarchy: created, attached, and destroyed with the operator, which then holds its only reference.  The
+      operator changes only when everything is in order */
+   primme_amd_amg_hierarchy *h = NULL;
+   if (amg_hierarchy_build(op, rowptr_host, colind_host, values_host, omega != 0.0, theta, omega, shift, 0, 1, &h)) return -1;
+   const int rc = primme_amd_operator_set_amg_hierarchy(op, h, smooth_steps, coarse_steps, over);
+   primme_amd_amg_hierarchy_destroy(h);
+   return rc ? -1 : 0;
 }
 
 extern "C" int primme_amd_operator_set_amg(primme_amd_operator *op, const int32_t *rowptr_host, const int32_t *colind_host,
@@ -710,11 +984,11 @@ struct amg_run {
 static void amg_product(amg_run *r, int l, const char *y, int64_t ldy, char *w, int64_t ldw) {
    if (r->rc) return;
    amg_state *s = &r->op->amg;
-   if (l > 0) r->rc = hipk_csr_matvec(s->lv[l].M, r->stream, y, ldy, w, ldw, r->nc);
-   else if (s->shift == 0.0) r->rc = hipk_csr_matvec(r->op->A, r->stream, y, ldy, w, ldw, r->nc);
+   if (l > 0) r->rc = hipk_csr_matvec(s->h->lv[l].M[s->dti], r->stream, y, ldy, w, ldw, r->nc);
+   else if (s->h->shift == 0.0) r->rc = hipk_csr_matvec(r->op->A, r->stream, y, ldy, w, ldw, r->nc);
    else {
       double ms[HIPK_CHEB_MAXCOLS];
-      for (int c = 0; c < r->nc; c++) ms[c] = -s->shift;
+      for (int c = 0; c < r->nc; c++) ms[c] = -s->h->shift;
       r->rc = hipk_csr_matvec_shifted(r->op->A, r->stream, y, ldy, w, ldw, r->nc, ms);
    }
    g_amg_launches++;
@@ -722,7 +996,7 @@ static void amg_product(amg_run *r, int l, const char *y, int64_t ldy, char *w, 
 static void amg_update(amg_run *r, int l, const hipk_cheb_coef *cf, int with_dinv, const char *x, int64_t ldx, const char *w, int64_t ldw,
       const char *yk, int64_t ldk, const char *yp, int64_t ldp, char *out, int64_t ldo) {
    if (r->rc) return;
-   const amg_level_dev *L = &r->op->amg.lv[l];
+   const amg_level_dev *L = &r->op->amg.h->lv[l];
    r->rc = hipk_amg_smooth_update(r->stream, r->dt, L->n, r->nc, cf, with_dinv ? L->dinv : NULL, x, ldx, w, ldw, yk, ldk, yp, ldp, out, ldo);
    g_amg_launches++;
 }
@@ -730,7 +1004,7 @@ static void amg_update(amg_run *r, int l, const hipk_cheb_coef *cf, int with_din
  * product in W: from zero when from < 0 (the result in Y[to]), else from Y[from].  Returns the panel of the last iterate. */
 static int amg_cheb(amg_run *r, int l, int steps, const char *b, int64_t lb, char *const Y[2], const int64_t LY[2], char *W, int64_t ldw,
       int from, int to) {
-   const double hi = r->op->amg.lv[l].rho, lo = 0.25 * hi, tb = 0.5 * (hi + lo), dl = 0.5 * (hi - lo);
+   const double hi = r->op->amg.h->lv[l].rho, lo = 0.25 * hi, tb = 0.5 * (hi + lo), dl = 0.5 * (hi - lo);
    hipk_cheb_coef cf;
    double rho = dl / tb;
    int cur, first = 1;
@@ -762,16 +1036,16 @@ static int amg_cheb(amg_run *r, int l, int steps, const char *b, int64_t lb, cha
 /* panel q of level l: level 0 has q = 0 (iterate) and 1 (product); the others 0 (right-hand side), 1, 2 (iterates), 3 (product) */
 static char *amg_panel(const amg_state *s, size_t es, int l, int q) {
    size_t off = 0;
-   for (int k = 0; k < l; k++) off += (size_t)s->lv[k].ld * (k == 0 ? 2 : 4);
-   return (char *)s->buf + (off + (size_t)s->lv[l].ld * q) * s->cols * es;
+   for (int k = 0; k < l; k++) off += (size_t)s->h->lv[k].ld * (k == 0 ? 2 : 4);
+   return (char *)s->buf + (off + (size_t)s->h->lv[l].ld * q) * s->cols * es;
 }
 /* the cycle at level l for the right-hand side b; the result goes to Y[0] */
 static void amg_vcycle(amg_run *r, int l, const char *b, int64_t lb, char *const Y[2], const int64_t LY[2], char *W, int64_t ldw) {
    amg_state *s = &r->op->amg;
-   const amg_level_dev *L = &s->lv[l];
-   if (l == s->nlev - 1) {
-      if (s->G) {
-         if (!r->rc) { r->rc = hipk_amg_dense_apply(r->stream, r->dt, (int)L->n, s->G, r->nc, b, lb, Y[0], LY[0]); g_amg_launches++; }
+   const amg_level_dev *L = &s->h->lv[l];
+   if (l == s->h->nlev - 1) {
+      if (s->h->G) {
+         if (!r->rc) { r->rc = hipk_amg_dense_apply(r->stream, r->dt, (int)L->n, s->h->G, r->nc, b, lb, Y[0], LY[0]); g_amg_launches++; }
       } else (void)amg_cheb(r, l, s->cs, b, lb, Y, LY, W, ldw, -1, 0);
       return;
    }
@@ -782,7 +1056,7 @@ static void amg_vcycle(amg_run *r, int l, const char *b, int64_t lb, char *const
    for (int c = 0; c < r->nc; c++) { cf.cx[c] = 1.0; cf.cw[c] = -1.0; }
    amg_product(r, l, Y[a], LY[a], W, ldw);
    amg_update(r, l, &cf, 0, b, lb, W, ldw, NULL, 0, NULL, 0, W, ldw);
-   const int64_t ldc = s->lv[l + 1].ld, LYc[2] = {ldc, ldc};
+   const int64_t ldc = s->h->lv[l + 1].ld, LYc[2] = {ldc, ldc};
    char *bc = amg_panel(s, r->es, l + 1, 0), *Wc = amg_panel(s, r->es, l + 1, 3);
    char *const Yc[2] = {amg_panel(s, r->es, l + 1, 1), amg_panel(s, r->es, l + 1, 2)};
    /* smoothed aggregation: R_l = P_l' and P_l in CSR; plain aggregation: the aggregate maps */
@@ -804,7 +1078,7 @@ extern "C" void primme_amd_amg_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME
       int *blockSize, struct primme_params *primme, int *ierr) {
    primme_amd_operator *op = (primme_amd_operator *)primme->preconditioner;
    void *stream = primme->queue ? (void *)*(hipStream_t *)primme->queue : NULL;
-   if (!op || op->amg.nlev < 1) { *ierr = 1; return; }
+   if (!op || !op->amg.h) { *ierr = 1; return; }
    *ierr = 0;
    if (*blockSize <= 0) return;
    if (!stream) stream = hipk_ctx_stream(hipk_csr_ctx(op->A));
@@ -815,19 +1089,19 @@ extern "C" void primme_amd_amg_precond(void *x, PRIMME_INT *ldx, void *y, PRIMME
    if (want > s->cols) {                           /* scratch for the widest chunk seen */
       if (s->buf) (void)hipFree(s->buf);
       s->buf = NULL; s->cols = 0;
-      size_t elems = 2 * (size_t)s->lv[0].ld;
-      for (int l = 1; l < s->nlev; l++) elems += 4 * (size_t)s->lv[l].ld;
+      size_t elems = 2 * (size_t)s->h->lv[0].ld;
+      for (int l = 1; l < s->h->nlev; l++) elems += 4 * (size_t)s->h->lv[l].ld;
       if (hipMalloc(&s->buf, elems * r.es * want) != hipSuccess) { *ierr = 1; return; }
       s->cols = want;
    }
-   g_amg_levels = s->nlev;
+   g_amg_levels = s->h->nlev;
    for (int c0 = 0; c0 < *blockSize && !r.rc; c0 += HIPK_CHEB_MAXCOLS) {
       r.nc = *blockSize - c0 < HIPK_CHEB_MAXCOLS ? *blockSize - c0 : HIPK_CHEB_MAXCOLS;
       const char *xc = (const char *)x + (size_t)c0 * *ldx * r.es;
       char *const Y[2] = {(char *)y + (size_t)c0 * *ldy * r.es, amg_panel(s, r.es, 0, 0)};
-      const int64_t LY[2] = {*ldy, s->lv[0].ld};
+      const int64_t LY[2] = {*ldy, s->h->lv[0].ld};
       g_amg_applies += r.nc;
-      amg_vcycle(&r, 0, xc, *ldx, Y, LY, amg_panel(s, r.es, 0, 1), s->lv[0].ld);
+      amg_vcycle(&r, 0, xc, *ldx, Y, LY, amg_panel(s, r.es, 0, 1), s->h->lv[0].ld);
    }
    if (r.rc) *ierr = 1;
 }

@@ -20,6 +20,7 @@
 #include <string.h>
 #include "primme_amd_io.h"
 #include "primme_amd.h"
+#include "amg_internal.h"
 
 void primme_amd_host_free(void *p) { free(p); }
 
@@ -489,7 +490,7 @@ static int amg_i32_cmp(const void *a, const void *b) {
 }
 
 /* dg = diag(M_l); dinv and rho of the level.  -1: a row without a diagonal entry or with m_ii <= 0, -5: out of memory */
-static int amg_level_finish(primme_amd_amg_level *L, double *dg) {
+int pa_amg_level_finish(primme_amd_amg_level *L, double *dg) {
    L->dinv = (double *)malloc(sizeof(double) * (size_t)L->n);
    if (!L->dinv) return -5;
    double rho = 0.0;
@@ -509,7 +510,7 @@ static int amg_level_finish(primme_amd_amg_level *L, double *dg) {
 }
 
 /* the three passes; agg[n] receives the aggregate of every row, returns the number of aggregates.  tmp: n int32 */
-static int64_t amg_aggregate(const primme_amd_amg_level *L, const double *dg, double theta, int32_t *agg, int32_t *tmp) {
+int64_t pa_amg_aggregate(const primme_amd_amg_level *L, const double *dg, double theta, int32_t *agg, int32_t *tmp) {
    const int64_t n = L->n;
    const int32_t *rp = L->rowptr, *ci = L->colind;
    const double *va = L->values;
@@ -550,6 +551,51 @@ static int64_t amg_aggregate(const primme_amd_amg_level *L, const double *dg, do
    }
 #undef AMG_STRONG
    return nc;
+}
+
+/* level 0 of a plan in L (zeroed): M_0 = A + shift I in double, the shift on the first diagonal entry of a row; dinv, rho and
+ * dg = diag(M_0).  -1: an index out of range, a row without a diagonal entry or m_ii <= 0; -5: out of memory */
+int pa_amg_level0(int64_t n, const int32_t *rowptr, const int32_t *colind, const void *values, size_t elem_size, double shift,
+      primme_amd_amg_level *L, double *dg) {
+   const int64_t nnz = rowptr[n];
+   int rc = 0;
+   L->n = n; L->nnz = nnz;
+   L->rowptr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+   L->colind = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1));
+   L->values = (double *)malloc(sizeof(double) * (size_t)(nnz > 0 ? nnz : 1));
+   if (!L->rowptr || !L->colind || !L->values) return -5;
+   memcpy(L->rowptr, rowptr, sizeof(int32_t) * (size_t)(n + 1));
+   memcpy(L->colind, colind, sizeof(int32_t) * (size_t)nnz);
+   for (int64_t q = 0; q < nnz; q++) L->values[q] = elem_size == 8 ? ((const double *)values)[q] : (double)((const float *)values)[q];
+   for (int64_t i = 0; i < n && !rc; i++) {          /* + shift on the (first) diagonal entry of the row */
+      int32_t q = rowptr[i];
+      while (q < rowptr[i + 1] && (colind[q] < 0 || colind[q] >= n || colind[q] != i)) {
+         if (colind[q] < 0 || colind[q] >= n) rc = -1;
+         q++;
+      }
+      for (int32_t r = q; r < rowptr[i + 1]; r++)
+         if (colind[r] < 0 || colind[r] >= n) rc = -1;
+      if (q < rowptr[i + 1]) L->values[q] += shift; else rc = -1;
+   }
+   return rc ? rc : pa_amg_level_finish(L, dg);
+}
+
+/* the aggregates of level L (pa_amg_aggregate) and their inverse map: sets nc, agg, aggptr and aggrows.  1: the aggregation
+ * would keep more than 0.8 n rows and is discarded, L as it was; -5: out of memory.  tmp: n int32 */
+int pa_amg_level_aggregate(primme_amd_amg_level *L, const double *dg, double theta, int32_t *tmp) {
+   int32_t *agg = (int32_t *)malloc(sizeof(int32_t) * (size_t)L->n);
+   if (!agg) return -5;
+   const int64_t nc = pa_amg_aggregate(L, dg, theta, agg, tmp);
+   if ((double)nc > 0.8 * (double)L->n) { free(agg); return 1; }
+   L->agg = agg; L->nc = nc;
+   L->aggptr = (int32_t *)calloc((size_t)(nc + 1), sizeof(int32_t));
+   L->aggrows = (int32_t *)malloc(sizeof(int32_t) * (size_t)L->n);
+   if (!L->aggptr || !L->aggrows) return -5;
+   for (int64_t i = 0; i < L->n; i++) L->aggptr[agg[i] + 1]++;
+   for (int64_t j = 0; j < nc; j++) L->aggptr[j + 1] += L->aggptr[j];
+   for (int64_t j = 0; j < nc; j++) tmp[j] = L->aggptr[j];
+   for (int64_t i = 0; i < L->n; i++) L->aggrows[tmp[agg[i]]++] = (int32_t)i;
+   return 0;
 }
 
 /* C = P' F P for the aggregates of F (F->nc, agg, aggptr, aggrows are set): row I adds the rows of aggregate I in ascending
@@ -601,7 +647,7 @@ static int amg_galerkin(const primme_amd_amg_level *F, primme_amd_amg_level *Cl)
  * the sums s_J of m_iq over the entries q with agg[col q] = J, in the row's order, then p_iJ = [J = agg[i]] - (omega / rho)
  * dinv_i s_J; columns sorted, one entry per position, an entry that cancels to zero stays.  R by a counting sort over the
  * columns of P: rows of R have ascending column indices and the bits of P. */
-static int amg_prolongation(const primme_amd_amg_level *F, double omega, primme_amd_amg_transfer *X) {
+int pa_amg_prolongation(const primme_amd_amg_level *F, double omega, primme_amd_amg_transfer *X) {
    const int64_t n = F->n, nc = F->nc;
    const double w = omega / F->rho;
    int rc = 0;
@@ -659,7 +705,7 @@ static int amg_prolongation(const primme_amd_amg_level *F, double omega, primme_
  * in their order, the entries (k, m) of row i of F in theirs and the entries (J, p) of row k of P with J >= I in theirs,
  * c_IJ += (r m) p; columns sorted, one entry per position.  Entry (J, I) then takes the bits of (I, J): C is exactly
  * symmetric.  -4 when C would have more than INT32_MAX entries. */
-static int amg_galerkin_general(const primme_amd_amg_level *F, const primme_amd_amg_transfer *X, primme_amd_amg_level *Cl) {
+int pa_amg_galerkin_general(const primme_amd_amg_level *F, const primme_amd_amg_transfer *X, primme_amd_amg_level *Cl) {
    const int64_t nc = F->nc;
    int rc = 0;
    int64_t cap = F->nnz > 16 ? F->nnz : 16, unnz = 0;
@@ -743,53 +789,21 @@ static int amg_plan_build(int64_t n, const int32_t *rowptr, const int32_t *colin
    int32_t *tmp = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
    int rc = (P && dg && tmp) ? 0 : -5;
    if (!rc) {
-      primme_amd_amg_level *L = &P->level[0];
-      const int64_t nnz = rowptr[n];
       P->shift = shift; P->theta = theta; P->omega = omega;
-      L->n = n; L->nnz = nnz;
-      L->rowptr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
-      L->colind = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1));
-      L->values = (double *)malloc(sizeof(double) * (size_t)(nnz > 0 ? nnz : 1));
-      if (!L->rowptr || !L->colind || !L->values) rc = -5;
-      else {
-         memcpy(L->rowptr, rowptr, sizeof(int32_t) * (size_t)(n + 1));
-         memcpy(L->colind, colind, sizeof(int32_t) * (size_t)nnz);
-         for (int64_t q = 0; q < nnz; q++) L->values[q] = elem_size == 8 ? ((const double *)values)[q] : (double)((const float *)values)[q];
-         for (int64_t i = 0; i < n && !rc; i++) {          /* + shift on the (first) diagonal entry of the row */
-            int32_t q = rowptr[i];
-            while (q < rowptr[i + 1] && (colind[q] < 0 || colind[q] >= n || colind[q] != i)) {
-               if (colind[q] < 0 || colind[q] >= n) rc = -1;
-               q++;
-            }
-            for (int32_t r = q; r < rowptr[i + 1]; r++)
-               if (colind[r] < 0 || colind[r] >= n) rc = -1;
-            if (q < rowptr[i + 1]) L->values[q] += shift; else rc = -1;
-         }
-      }
-      if (!rc) rc = amg_level_finish(L, dg);
+      rc = pa_amg_level0(n, rowptr, colind, values, elem_size, shift, &P->level[0], dg);
    }
    int l = 0;
    while (!rc) {
       primme_amd_amg_level *L = &P->level[l];
       if (L->n <= PRIMME_AMD_AMG_DENSE_ROWS || l + 1 >= PRIMME_AMD_AMG_MAXLEVELS) break;
-      int32_t *agg = (int32_t *)malloc(sizeof(int32_t) * (size_t)L->n);
-      if (!agg) { rc = -5; break; }
-      const int64_t nc = amg_aggregate(L, dg, theta, agg, tmp);
-      if ((double)nc > 0.8 * (double)L->n) { free(agg); break; }         /* stalled: this level is the last */
-      L->agg = agg; L->nc = nc;
-      L->aggptr = (int32_t *)calloc((size_t)(nc + 1), sizeof(int32_t));
-      L->aggrows = (int32_t *)malloc(sizeof(int32_t) * (size_t)L->n);
-      if (!L->aggptr || !L->aggrows) { rc = -5; break; }
-      for (int64_t i = 0; i < L->n; i++) L->aggptr[agg[i] + 1]++;
-      for (int64_t j = 0; j < nc; j++) L->aggptr[j + 1] += L->aggptr[j];
-      for (int64_t j = 0; j < nc; j++) tmp[j] = L->aggptr[j];
-      for (int64_t i = 0; i < L->n; i++) L->aggrows[tmp[agg[i]]++] = (int32_t)i;
+      rc = pa_amg_level_aggregate(L, dg, theta, tmp);
+      if (rc) { rc = rc > 0 ? 0 : rc; break; }                           /* 1: stalled, this level is the last */
       if (omega == 0.0) rc = amg_galerkin(L, &P->level[l + 1]);
       else {
-         rc = amg_prolongation(L, omega, &P->transfer[l]);
-         if (!rc) rc = amg_galerkin_general(L, &P->transfer[l], &P->level[l + 1]);
+         rc = pa_amg_prolongation(L, omega, &P->transfer[l]);
+         if (!rc) rc = pa_amg_galerkin_general(L, &P->transfer[l], &P->level[l + 1]);
       }
-      if (!rc) rc = amg_level_finish(&P->level[l + 1], dg);
+      if (!rc) rc = pa_amg_level_finish(&P->level[l + 1], dg);
       l++;
    }
    free(dg); free(tmp);

@@ -8,6 +8,8 @@ per invocation, so that a job runs each under a time limit of its own and chains
     python scripts/amg_headline.py --case lap   --config multigrid
     python scripts/amg_headline.py --case lap   --config amg
     python scripts/amg_headline.py --case lap   --config amg_smoothed # smoothed aggregation; also for --case lunda
+    python scripts/amg_headline.py --case lap   --config amg_hierarchy # one hierarchy built on the device, two solves on it (4q);
+                                                                      # also for --case lunda
 
 Every invocation adds (or replaces) its row in profiles/amg_headline.json (--out): the seconds of each of --repeats solves
 after a short warm-up solve of the same configuration, their median, outer iterations, matvecs, the preconditioner's counters
@@ -71,7 +73,7 @@ def host_setup(lib, rp, ci, va, shift=0.0, theta=0.08, omega=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", choices=("lunda", "lap"), required=True)
-    ap.add_argument("--config", choices=("none", "jacobi", "chebyshev", "multigrid", "amg", "amg_smoothed"), required=True)
+    ap.add_argument("--config", choices=("none", "jacobi", "chebyshev", "multigrid", "amg", "amg_smoothed", "amg_hierarchy"), required=True)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--max-outer", type=int, default=60000)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "amg_headline.json"))
@@ -102,6 +104,7 @@ def main():
         workload = f"CSR 5-point Laplacian {dims[0]} x {dims[1]}, 10 smallest, GD+k, block 1, eps 1e-8 |A|"
         allowed = {"none": ("none", None), "chebyshev": ("chebyshev steps=16", "chebyshev"), "multigrid": ("multigrid V(2,2)", ("multigrid", dims, 2, 16)),
                    "amg": ("amg V(2,2)", ("amg",)), "amg_smoothed": ("amg smoothed V(2,2)", ("amg_smoothed",))}
+    allowed["amg_hierarchy"] = ("amg hierarchy, device set-up, V(2,2)", ("amg_hierarchy",))
     if a.config not in allowed:
         raise SystemExit(f"case {a.case} has the configurations {sorted(allowed)}")
     doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
@@ -120,6 +123,49 @@ def main():
         row.update(setup_seconds_host=secs, level_rows=lrows, levels=len(lrows), operator_complexity=cx)
         print(json.dumps(row), flush=True)
     kw["maxOuterIterations"] = a.max_outer
+    if a.config == "amg_hierarchy":
+        # the host set-up by itself, then per repeat ONE hierarchy built on the device (whole call, device stages,
+        # per stage and level; the host's remainder is the aggregate and download lines) and two solves on it; to be read against
+        # the "amg smoothed V(2,2)" row, whose every solve includes the host set-up and the upload
+        from primme_amd.api import AmgHierarchy
+        secs, lrows, cx = host_setup(lib, rp, ci, va, omega=4.0 / 3.0)
+        row.update(setup_seconds_host=secs, level_rows_host=lrows)
+        s = Session(Operator(n, csr=(rp, ci, va)))
+        # the host's stages per level: the same build with every level sent to the host routines (entry limit 0); the lines are
+        # P with its transpose, the triple product, the finish, and the upload in the place of the download
+        os.environ["PRIMME_AMD_AMG_SETUP_MAX_ENTRIES"] = "0"
+        Hh = AmgHierarchy(s, setup="device")
+        del os.environ["PRIMME_AMD_AMG_SETUP_MAX_ENTRIES"]
+        assert Hh.fallback_levels == Hh.levels - 1
+        row.update(host_route_per_level=dict(setup_seconds=Hh.setup_seconds, level_rows=Hh.rows, level_nnz=Hh.nnz, stage_seconds=Hh.stage_seconds))
+        Hh.close()
+        print(json.dumps(row), flush=True)
+        builds, first, second = [], [], []
+        for _ in range(a.repeats):
+            H = AmgHierarchy(s, setup="device")
+            builds.append(dict(setup_seconds=H.setup_seconds, device_seconds=H.device_seconds, fallback_levels=H.fallback_levels,
+                               level_rows=H.rows, level_nnz=H.nnz, stage_seconds=H.stage_seconds))
+            for out in (first, second):
+                t0 = time.perf_counter()
+                r = s.solve(precond=("amg_hierarchy", H), **kw)
+                out.append(time.perf_counter() - t0)
+            H.close()
+        s.close()
+        ev = np.sort(r.evals)
+        med = sorted(builds, key=lambda b: b["setup_seconds"])[len(builds) // 2]
+        row.update(ret=r.ret, converged_pairs=int(r.initSize), builds=builds, setup_seconds_device_route_median=med["setup_seconds"],
+                   device_stage_seconds_median_build=med["device_seconds"],
+                   host_remainder_seconds_median_build=dict(aggregate=sum(x["aggregate"] for x in med["stage_seconds"]),
+                                                            download=sum(x["download"] for x in med["stage_seconds"])),
+                   seconds_first_solve=first, seconds_second_solve=second, seconds_first_solve_median=float(np.median(first)),
+                   seconds_second_solve_median=float(np.median(second)), outer_iterations=r.stats["numOuterIterations"],
+                   matvecs=r.stats["numMatvecs"], precond_stats=r.precond_stats,
+                   max_eval_error_vs_truth=float(np.max(np.abs(ev - exact[:len(ev)]))) if r.ret == 0 else None, evals=ev.tolist())
+        rows[:] = [x for x in rows if x["label"] != label] + [row]
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        json.dump(doc, open(a.out, "w"), indent=1)
+        print(json.dumps({k: v for k, v in row.items() if k not in ("evals", "builds")}), flush=True)
+        return
     s = Session(Operator(n, csr=(rp, ci, va)))
     s.solve(precond=precond, **dict(kw, maxOuterIterations=min(20, a.max_outer)))      # warm-up, not timed
     secs = []
